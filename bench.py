@@ -19,6 +19,18 @@ reference's own arithmetic; r101: ``fp32``) under ``other_parity_modes``.
 Contract: ``python bench.py --gpus N --steps K --warmup W``; rank 0 prints ONE JSON line.  N > 1: either started under
 ``python -m torch.distributed.run`` (RANK / WORLD_SIZE in the environment), or plainly -- then the script starts the N
 ranks itself in a child process before touching the GPU (simple-sfod_amd/launch.py).
+
+A plain run does what the headline needs and nothing else: set-up (incl. the planted head's calibration), W warm-up steps,
+K timed steps, the outputs of the last timed step if ``--dump-outputs DIR`` is given, the result line.  Everything else
+the line can carry is measured only with ``--full``: the roofline / per-kernel segment, the host-enqueue check
+(``gpu_fill``), the other precisions and shapes (child processes), the CPU baseline, rocm-smi clock / power samples and,
+for N > 1, the exchange block and RCCL's per-rank log.
+
+``--dump-outputs DIR``: what the last timed step computed, as ``DIR/<name>.npy`` (float32, scalars float64): its logged
+scalars (losses, pseudo-label statistics), the pseudo labels the teacher handed to the student, and a fixed seeded
+sample of the student's parameters and gradient and of the teacher's parameters (+ both BatchNorm statistics).  Inputs
+are seeded and every run's step sums its gradients in a fixed order (SFOD.DETERMINISTIC, see build_trainer), so two runs
+with the same arguments write bit-identical files and two builds can be compared file by file.
 """
 import argparse
 import importlib
@@ -204,7 +216,13 @@ def _launcher():
 
 def build_trainer(sfod, args, dtype, world, rank, local_rank):
     import torch
-    opts = ["OUTPUT_DIR", "", "SFOD.COMPUTE_DTYPE", dtype, "SOLVER.CHECKPOINT_PERIOD", "0",
+    # SFOD.DETERMINISTIC: the same step with every gradient sum in a fixed order (slabs instead of float atomics), so a run
+    # with the same arguments computes the same bits every time.  With the atomics two runs differ in the last bits and
+    # self-training on its own pseudo labels grows that into other pseudo labels and losses within a hundred steps (the
+    # planted-workload check itself can fail on it).  Cost, same box, alternating: 0.4 % of the headline's images/s, 0.7 %
+    # for --model r101, 0.9 % for --trainer base (the slab pass over the split partials); ``--opts SFOD.DETERMINISTIC
+    # False`` times the atomics, the mode of the figures recorded before this choice.
+    opts = ["OUTPUT_DIR", "", "SFOD.COMPUTE_DTYPE", dtype, "SOLVER.CHECKPOINT_PERIOD", "0", "SFOD.DETERMINISTIC", "True",
             "SFOD.SYNTHETIC.NUM_IMAGES", str(max(16, 2 * args.batch)), "MODEL.DEVICE", f"cuda:{local_rank}",
             "TEST.EVAL_PERIOD", "0", "TEST.VAL_LOSS", "False"]
     if args.trainer == "base":
@@ -257,6 +275,61 @@ class StepLog:
 
 STEP_LOG = None
 CHECK_WINDOW = 120      # logged steps (warm-up + timed) the planted-workload check covers
+DUMP_SAMPLE = 1 << 21   # --dump-outputs: elements sampled from each large flat buffer (8 MB in float32)
+
+
+def record_pseudo_labels(trainer):
+    """Keep the pseudo labels of the latest teacher pass on ``trainer._last_pseudo`` (for --dump-outputs): the trainer's
+    own ``_teacher_pass``, its result kept by reference -- no copy, no synchronisation."""
+    inner = trainer._teacher_pass
+
+    def teacher_pass(*a, **k):
+        trainer._last_pseudo = inner(*a, **k)
+        return trainer._last_pseudo
+    trainer._teacher_pass = teacher_pass
+
+
+def dump_outputs(trainer, out_dir):
+    """What the last step computed, as ``out_dir/<name>.npy``; call right after the timed steps' final synchronisation,
+    before anything else runs on the trainer."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t, dtype=np.float32):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().double().numpy().astype(dtype))
+
+    # the step's logged device scalars: weighted losses, total_loss, pseudo-label counts, mean teacher confidence
+    for k, v in sorted(trainer.storage._pending.items()):
+        if isinstance(v, torch.Tensor):
+            save(k.replace("/", "."), v.reshape(()), np.float64)
+    pseudo = trainer.__dict__.get("_last_pseudo")
+    if pseudo is not None:
+        count = pseudo.count.long()
+        live = torch.arange(pseudo.boxes.shape[1], device=count.device)[None, :] < count[:, None]      # [B, G]
+        save("pseudo_count", count)
+        save("pseudo_boxes", pseudo.boxes * live[..., None])
+        save("pseudo_classes", pseudo.classes * live)
+        if pseudo.scores is not None:
+            s = pseudo.scores[:, :live.shape[1]]
+            save("pseudo_scores", s * live[:, :s.shape[1]])
+
+    def sample(buf, seed):
+        """the whole buffer, or DUMP_SAMPLE positions of it drawn by a fixed generator (sorted, the same for every run)"""
+        n = buf.numel()
+        if n <= DUMP_SAMPLE:
+            return buf
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+        return buf[idx.to(buf.device)]
+
+    opt = trainer.optimizer
+    save("student_params", sample(opt.flat.param, 0))
+    save("student_grad", sample(opt.flat.grad, 0))
+    save("student_bn_stats", sample(opt.flat.fbuf, 1))
+    teacher = getattr(opt, "teacher", None)
+    if teacher is not None:     # same layout as the student's (FusedSGD.attach_teacher): the same positions
+        save("teacher_params", sample(teacher.param, 0))
+        save("teacher_bn_stats", sample(teacher.fbuf, 1))
 
 
 def run_steps(trainer, first_iter, n):
@@ -301,10 +374,19 @@ def main():
     ap.add_argument("--opts", nargs="*", default=[], help="extra KEY VALUE config overrides (A/B runs)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="teacher pass on the main stream (SFOD.OVERLAP_TEACHER False)")
-    ap.add_argument("--kernel-table", action="store_true", help="stderr: per-shape table of the MFMA kernels")
+    ap.add_argument("--kernel-table", action="store_true", help="stderr: per-shape table of the MFMA kernels (with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / per-kernel figures, gpu_fill, the other "
+                         "precisions and shapes, the CPU baseline, rocm-smi samples, the N > 1 exchange block (the --no-* "
+                         "options switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (losses, pseudo labels, a fixed sample "
+                         "of the student / teacher parameters and the student gradient)")
     args = ap.parse_args()
     if args.dtype is None:
         args.dtype = PARITY_DTYPE[args.model]
+    if args.kernel_table and not args.full:
+        ap.error("--kernel-table needs --full")
     t_start = time.perf_counter()
 
     def note(msg):      # progress on stderr (the JSON line is the only thing on stdout)
@@ -335,12 +417,14 @@ def main():
         if one_gpu:
             dist.init_process_group("gloo")
         else:
-            # RCCL's INFO lines (INIT / GRAPH / TUNING) of every rank go to a per-rank file: rank 0's is summarised in
-            # the line (algorithm / protocol per payload, channels, transports) so that a scaling run explains itself
-            rccl_log = telemetry.rccl_debug_setup(rank)
+            # --full: RCCL's INFO lines (INIT / GRAPH / TUNING) of every rank go to a per-rank file: rank 0's is summarised
+            # in the line (algorithm / protocol per payload, channels, transports) so that a scaling run explains itself
+            if args.full:
+                rccl_log = telemetry.rccl_debug_setup(rank)
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    # clocks and package power of every GPU of the node beside the run (rank 0: a host thread running rocm-smi)
-    smi = telemetry.SmiSampler().start() if rank == 0 and not args.no_smi and not telemetry.under_profiler() else None
+    # --full: clocks and package power of every GPU of the node beside the run (rank 0: a host thread running rocm-smi)
+    smi = (telemetry.SmiSampler().start() if args.full and rank == 0 and not args.no_smi and not telemetry.under_profiler()
+           else None)
 
     note("torch imported")
     sfod = importlib.import_module("simple-sfod_amd")
@@ -364,14 +448,17 @@ def main():
                 dist.broadcast(bp.cls_score.bias, 0)
                 trainer._copy_main_model()
     STEP_LOG = StepLog()
+    if args.dump_outputs and args.trainer != "base":
+        record_pseudo_labels(trainer)
     run_steps(trainer, 0, args.warmup)
-    # Per-kernel HIP-event timing is only meaningful when kernels do not share the GPU: with
+    # --full: per-kernel HIP-event timing is only meaningful when kernels do not share the GPU: with
     # SFOD.OVERLAP_TEACHER the teacher pass runs on a second stream beside the student's forward, so the
     # roofline figures come from a short single-stream segment AFTER the timed region (same model, same
     # shapes, same kernels); without overlap they are measured inside the timed region itself.
     overlapped = bool(cfg.SFOD.OVERLAP_TEACHER) and not args.no_overlap and args.trainer != "base"
+    kernel_timer = args.full and not args.no_kernel_timer
     timer = None
-    if not args.no_kernel_timer and not overlapped:
+    if kernel_timer and not overlapped:
         timer = sfod.native.KernelTimer()
         sfod.native.set_timer(timer)
     sync()
@@ -380,9 +467,12 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     sfod.native.set_timer(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, args.dump_outputs)
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
     step_log, STEP_LOG = STEP_LOG, None        # warm-up + timed steps; the measurement segments below are not logged
     rl_steps, rl_elapsed, rl_segment = args.steps, elapsed, "the timed region"
-    if not args.no_kernel_timer and overlapped:
+    if kernel_timer and overlapped:
         rl_steps = max(1, min(5, args.steps))
         trainer.overlap_teacher = False
         bbs = [m.backbone for m in (trainer.model, getattr(trainer, "model_teacher", None)) if m is not None]
@@ -411,7 +501,7 @@ def main():
     # library: the share of the step's wall time its own launches cover -- the rest is torch's small kernels
     # (tools/profile_torch_ops.py lists them) plus idle gaps.  N = 1 only.
     gpu_fill = None
-    if world == 1 and not args.no_kernel_timer:
+    if world == 1 and kernel_timer:
         n_id = max(1, min(5, args.steps))
         trainer.overlap_teacher = False
         bbs = [m.backbone for m in (trainer.model, getattr(trainer, "model_teacher", None)) if m is not None]
@@ -470,9 +560,9 @@ def main():
     rec = trainer.storage.flush()
     note(f"timed region done: {elapsed:.2f} s")
 
-    # ---- N > 1: what the exchange step costs (the flat-gradient all-reduce alone; the step without any exchange) ----
+    # ---- N > 1, --full: what the exchange step costs (the flat-gradient all-reduce alone; the step without any exchange) ----
     comm = None
-    if world > 1:
+    if world > 1 and args.full:
         flat = trainer.optimizer.flat
         for _ in range(3):
             dist.all_reduce(flat.grad)
@@ -549,7 +639,7 @@ def main():
               "f16x3": ["bf16x3", "bf16"] if args.model == "r101" else ["bf16"]}[args.dtype]
     others = OTHER_PARITY.get(args.model, {}).get(args.dtype, []) if args.trainer != "base" or args.model == "vgg" else []
     other_modes = []
-    if not args.no_secondary and (faster or others) and world == 1:
+    if args.full and not args.no_secondary and (faster or others) and world == 1:
         import subprocess
         n2 = max(5, min(40, args.steps))
         secondary = []
@@ -576,13 +666,13 @@ def main():
             secondary = secondary[0]
         elif not secondary:
             secondary = None
-    note("secondary block done")
+        note("secondary block done")
     # ---- the other shapes BASELINE.md section 3 names for this config (R600 AND RFULL, B = 1 AND B = 8 per GPU), measured by
-    # child processes of the default run like the other modes: 1024x2048 network tensors at B = 8, and the yaml's literal
+    # child processes of the --full run like the other modes: 1024x2048 network tensors at B = 8, and the yaml's literal
     # one frame per GPU (IMS_PER_BATCH_TARGET 1, reference yaml :33-46).  Same arithmetic mode, same planted head recipe.
     other_shapes = None
-    if (not args.no_secondary and not args.no_other_shapes and world == 1 and args.res == "r600" and args.batch == 8
-            and args.trainer != "base" and not args.opts):
+    if (args.full and not args.no_secondary and not args.no_other_shapes and world == 1 and args.res == "r600"
+            and args.batch == 8 and args.trainer != "base" and not args.opts):
         import subprocess
         other_shapes = []
         for label, extra in (("one frame per GPU (the yaml's IMS_PER_BATCH_TARGET 1), 600x1200 tensors",
@@ -594,8 +684,9 @@ def main():
                               "(the reference's hand-over: CPU uint8 tensors)",
                               ["--batch", "8", "--res", "r600", "--steps", str(args.steps), "--warmup", "5", "--host-frames"]),
                              )[:3 if args.model == "vgg" else 1]:
+            # (--full for the child's clock / power samples: everything else of it is switched off)
             cmd = [sys.executable, os.path.abspath(__file__), "--dtype", args.dtype, "--model", args.model, "--trainer", args.trainer,
-                   "--no-cpu-baseline", "--no-secondary", "--no-kernel-timer"] + extra
+                   "--full", "--no-cpu-baseline", "--no-secondary", "--no-kernel-timer"] + extra
             cmd += (["--no-planted"] if args.no_planted else [])
             cmd += ["--plant-scale", str(args.plant_scale)] if args.plant_scale else []
             try:
@@ -663,7 +754,7 @@ def main():
                                "frames resized once at start-up (Pillow), RandomFlip on the device every step"), "elide_zero_weight_branches": bool(cfg.SFOD.ELIDE_DEAD_BRANCHES),
             "planted_labels": planted if planted is not None else False,
             **(step_log.summary() if step_log is not None and args.trainer != "base" else {}),
-            "max_steps_in_flight": int(cfg.SFOD.MAX_STEPS_IN_FLIGHT),
+            "max_steps_in_flight": int(cfg.SFOD.MAX_STEPS_IN_FLIGHT), "deterministic": bool(cfg.SFOD.DETERMINISTIC),
             "algorithmic_tflop_per_image": round(sflops / 1e12, 3),
             # torch's caching allocator on this rank (the library allocates nothing itself): what the step holds of the 288 GB
             "peak_hbm_reserved_GB": round(torch.cuda.max_memory_reserved() / 1e9, 1),
@@ -777,7 +868,7 @@ def main():
                                      "peak": PEAK[args.dtype], "unit": "TFLOP/s",
                                      "frac": round(wk["flops"] / (wk["ms"] * 1e-3) / 1e12 / PEAK[args.dtype], 4),
                                      "share_of_step_time": round(wk["ms"] / (1000.0 * rl_elapsed), 4)}
-    if world == 1 and not args.no_cpu_baseline and args.trainer != "base":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.trainer != "base":
         note("cpu baseline ...")
         out["cpu_baseline"] = cpu_baseline(args.res, planted, args.model)
     note("done")

@@ -1947,15 +1947,53 @@ k_bias_grad(const T* __restrict__ dy, float* __restrict__ db, int M, int N, int 
   if (wave == 0 && n < N) atomicAdd(db + n, red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
 }
 
+// deterministic mode (sfod_set_deterministic): the same sums in the same order as one slice of k_bias_grad -- wave w of
+// the workgroup of 64 columns adds the rows w, w + 4, ... one after the other, the four partials are added in wave order
+// and the result onto db -- so the bits are those of the single-slice launch.  Only the loads differ: BGD_AHEAD rows are
+// fetched before they are added (one row at a time left the single workgroup latency-bound: ~0.4 ms per call at 5 000 rows).
+#define BGD_AHEAD 60
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_bias_grad_det(const T* __restrict__ dy, float* __restrict__ db, int M, int N, int ld, int accumulate) {
+  __shared__ float red[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = blockIdx.x * 64 + lane;
+  float acc = 0.f;
+  if (n < N) {
+    int m = wave;
+    for (; m + 4 * (BGD_AHEAD - 1) < M; m += 4 * BGD_AHEAD) {
+      float v[BGD_AHEAD];
+#pragma unroll
+      for (int u = 0; u < BGD_AHEAD; ++u) v[u] = to_f32(dy[(int64_t)(m + 4 * u) * ld + n]);
+#pragma unroll
+      for (int u = 0; u < BGD_AHEAD; ++u) acc += v[u];
+    }
+    for (; m < M; m += 4) acc += to_f32(dy[(int64_t)m * ld + n]);
+  }
+  red[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && n < N) db[n] = (accumulate ? db[n] : 0.f) + (red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
+}
+
 extern "C" int sfod_bias_grad(const void* dy, float* db, int M, int N, int ld, int accumulate, int dt,
                               void* stream) {
   SFOD_REQUIRE_EXTENTS("bias_grad", M, N, ld);
   hipStream_t s = (hipStream_t)stream;
-  if (!accumulate) (void)hipMemsetAsync(db, 0, sizeof(float) * N, s);
+  const bool det = sfod_deterministic() && M > 0 && N > 0;
+  if (!accumulate && !det) (void)hipMemsetAsync(db, 0, sizeof(float) * N, s);
   if (M == 0) return 0;
+  if (det) {
+    if (dt == SFOD_F32)
+      hipLaunchKernelGGL(k_bias_grad_det<float>, dim3(cdiv(N, 64)), dim3(256), 0, s, (const float*)dy, db, M,
+                         N, ld, accumulate);
+    else
+      hipLaunchKernelGGL(k_bias_grad_det<bf16_t>, dim3(cdiv(N, 64)), dim3(256), 0, s, (const bf16_t*)dy, db,
+                         M, N, ld, accumulate);
+    return sfod_check_launch("bias_grad");
+  }
   int slices = (M + 63) / 64;
   if (slices > BG_SLICES) slices = BG_SLICES;
-  if (sfod_deterministic()) slices = 1;      // one workgroup per 64 columns walks every row: a single add per address
   const int rps = (M + slices - 1) / slices;
   dim3 grid(cdiv(N, 64), cdiv(M, rps));
   if (dt == SFOD_F32)

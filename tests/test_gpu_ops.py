@@ -1100,3 +1100,37 @@ def test_nms_kernel_equals_the_independent_huggingface_implementation(native, n,
         c = keep_cnt[b].item()
         got = orders[b][keep_idx[b, :c].cpu().long()]
         assert 0 < len(keep_ref[b]) < n and got.tolist() == keep_ref[b].tolist()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_bias_grad_in_deterministic_mode_is_the_single_slice_sum_bit_for_bit(native, dtype):
+    """``sfod_bias_grad`` under ``sfod_set_deterministic``: no atomics, and the bits of the single-slice order -- wave w adds
+    the rows w, w + 4, ... in turn, the four partials are added in wave order and the result onto db -- restated here in
+    float32 on the host, with and without ``accumulate`` (row counts from a few to the RPN head's 5 328, strided rows,
+    column counts that do and do not fill a 64-column group); and within fp32 rounding of an fp64 reference."""
+
+    def single_slice(x, start):
+        parts = []
+        for w in range(4):
+            acc = np.zeros(x.shape[1], np.float32)
+            for row in x[w::4]:
+                acc = acc + row
+            parts.append(acc)
+        return start + (((parts[0] + parts[1]) + parts[2]) + parts[3])
+
+    prev = native.set_deterministic(True)
+    try:
+        g = torch.Generator().manual_seed(3)
+        for M, N, ld in ((5328, 75, 80), (4096, 1024, 1024), (37, 1, 8), (300, 130, 136), (255, 64, 64)):
+            dy = torch.randn(M, ld, generator=g).to(dtype).to(DEV)
+            x = dy[:, :N].float().cpu().numpy()
+            a = native.bias_grad(dy, N)
+            assert np.array_equal(a.cpu().numpy(), single_slice(x, np.float32(0))), (M, N, ld)
+            ref = dy[:, :N].double().sum(0)
+            tol = 1e-6 * dy[:, :N].double().abs().sum(0).max().item() + 1e-6
+            assert (a.double() - ref).abs().max().item() <= tol, (M, N, ld)
+            acc = a.clone()
+            native.bias_grad(dy, N, db=acc, accumulate=True)
+            assert np.array_equal(acc.cpu().numpy(), single_slice(x, a.cpu().numpy())), (M, N, ld)
+    finally:
+        native.set_deterministic(prev)

@@ -232,7 +232,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path, model):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "4",
-           "--model", model]
+           "--model", model, "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr.decode()[-4000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]

@@ -3,7 +3,7 @@
 # pmc:   rocprofv3 kernel trace + SQ counters + HBM traffic counters of the default bench workload (writes the traffic file
 #        bench.py reads, gpurun_out/<tag>_pmc_hbm_traffic.json -> copy to profiles/pmc_hbm_traffic_latest.json BEFORE the
 #        bench part so that the bench line carries it)
-# bench: the default bench line (with cpu_baseline and the secondary block) and the side configurations
+# bench: the --full bench line (with cpu_baseline and the secondary block) and the side configurations
 export TMPDIR=/tmp
 TAG=${1:-rX}; WHAT=${2:-all}
 O=gpurun_out
@@ -46,15 +46,15 @@ if [ "$WHAT" = all ] && [ -s $O/${TAG}_pmc_hbm_traffic_bf16x3.json ]; then
   fi
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
-  python3 bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
-  python3 bench.py --kernel-table --steps 30 --no-cpu-baseline --no-secondary > /dev/null 2> $O/${TAG}_kernel_table.txt
+  python3 bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+  python3 bench.py --full --kernel-table --steps 30 --no-cpu-baseline --no-secondary > /dev/null 2> $O/${TAG}_kernel_table.txt
   for cfg in "--trainer base" "--trainer base --res full --steps 40" "--res full --steps 40" "--batch 1 --steps 200" "--opts SFOD.ELIDE_DEAD_BRANCHES False" "--dtype f16x3"; do
     name=$(echo $cfg | tr -d ' -' | tr '.' '_')
     wait_vram
-    python3 bench.py $cfg --no-cpu-baseline --no-secondary > $O/${TAG}_bench_${name}.json 2> $O/${TAG}_bench_${name}.err
+    python3 bench.py $cfg --full --no-cpu-baseline --no-secondary > $O/${TAG}_bench_${name}.json 2> $O/${TAG}_bench_${name}.err
   done
   # config #5 with its labelled blocks (other parity mode fp32; reduced-precision bf16x3 / bf16) from child processes
-  python3 bench.py --model r101 --steps 40 --no-cpu-baseline > $O/${TAG}_bench_modelr101steps40.json 2> $O/${TAG}_bench_modelr101steps40.err
+  python3 bench.py --model r101 --steps 40 --full --no-cpu-baseline > $O/${TAG}_bench_modelr101steps40.json 2> $O/${TAG}_bench_modelr101steps40.err
 fi
 if [ "$WHAT" = r101 ] || [ "$WHAT" = all ]; then
   # config #5 in its parity mode (f16x3): kernel trace of single-stream steps, GPU busy fraction (union of kernel intervals
@@ -65,6 +65,6 @@ if [ "$WHAT" = r101 ] || [ "$WHAT" = all ]; then
   python3 tools/rocpd_stats.py $DB 15 > $O/${TAG}_r101_f16x3_kernel_stats.csv
   python3 tools/busy_fraction.py $DB 0.3 > $O/${TAG}_r101_f16x3_busy_fraction.txt
   rm -rf $O/prof_r101
-  python3 bench.py --model r101 --no-overlap --steps 20 --no-cpu-baseline --no-secondary > $O/${TAG}_bench_r101_f16x3_single_stream.json 2> /dev/null
+  python3 bench.py --model r101 --no-overlap --steps 20 --full --no-cpu-baseline --no-secondary > $O/${TAG}_bench_r101_f16x3_single_stream.json 2> /dev/null
 fi
 ls -la $O | grep ${TAG}_ | awk '{print $5, $9}'
