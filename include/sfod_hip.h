@@ -134,19 +134,26 @@ int sfod_conv_fwd_bnin_supported(int B, int H, int W, int Cin, int Cout, int dt)
 int sfod_conv_fwd_bnin(const float* x_pre, const float* in_mean, const float* in_invstd, const float* in_gamma,
                        const float* in_beta, const void* w, const float* bias, float* y, int B, int H, int W, int Cin,
                        int Cout, int ldy, int act, float* stats, int dt, void* stream);
-/* Tile shape of the generic implicit-GEMM kernel behind sfod_conv_fwd (1x1 / linear / first layer): 0 = the planner's choice
- * (environment SFOD_GEMM_TILE), 1 = 128 x 64, 2 = 128 x 128, 3 = 256 x 128, 4 = 256 x 64, 5 = 256 x 256 (pairs, fp32 out),
+/* Tile shape of the generic implicit-GEMM kernel behind sfod_conv_fwd (1x1 / linear / first layer), 0..8 (other values: 0):
+ * 0 = the planner's choice (environment SFOD_GEMM_TILE), 1 = 128 x 64, 2 = 128 x 128, 3 = 256 x 128, 4 = 256 x 64, 5 = 256 x 256 (pairs, fp32 out),
  * 6 / 7 / 8 = 256 x 128 / 128 x 128 / 256 x 128 (four stages) with 64-byte K stages (pairs, fp32 out: two or three
  * workgroups per CU); shapes a layer cannot take fall back to the planner's.  Every shape computes the same values.  For
  * A/B runs and parity tests. */
 int sfod_set_gemm_tile(int tile);
-/* workgroup shape of the halo-patch kernel: 0 auto, 1 = 512 px x 128 ch, 2 = 256 x 128, 3 = 256 x 64,
- * 4 = 512 x 64 (applied where the channel counts allow it), 5 = 256 x 128 on v_mfma_f32_16x16x32 (operand pairs with
- * Cin % 32 == 0; otherwise as 2: 8 waves x (64 px x 64 ch), four waves per SIMD), 6 = the same with 4 waves x (128 px x
- * 64 ch), two per SIMD (leaves registers for a co-resident kernel; tools/experiments/corun_conv_bn.py), 7 / 8 = shapes 3 / 4
- * on v_mfma_f32_16x16x32 (operand pairs with Cin % 32 == 0: 4 waves x (64 px x 64 ch) / 8 waves of them; otherwise as 3 / 4).
- * For A/B runs and parity tests. */
+/* workgroup shape of the halo-patch kernel, 0..9: 0 auto, 1 = 512 px x 128 ch, 2 = 256 x 128, 3 = 256 x 64,
+ * 4 = 512 x 64 (3 / 4 need physical Cin % 64 == 0, else they run as 2 / 1), 5 = 256 x 128 on v_mfma_f32_16x16x32 (operand
+ * pairs with logical Cin % 32 == 0; otherwise as 2: 8 waves x (64 px x 64 ch), four waves per SIMD), 6 = the same with 4
+ * waves x (128 px x 64 ch), two per SIMD (leaves registers for a co-resident kernel; tools/experiments/corun_conv_bn.py),
+ * 7 / 8 = shapes 3 / 4 on v_mfma_f32_16x16x32 (4 waves x (64 px x 64 ch) / 8 waves of them), 9 = shape 3 on it with 8 waves
+ * x (32 px x 64 ch), two workgroups = 16 waves per CU.  7 / 8 / 9 need operand pairs with physical Cin % 64 == 0 (logical
+ * Cin % 32 == 0); with fewer channels they run as the 32x32x16 kernel of shape 2 / 1 / 2, on other operands as 3 / 4 / 3.
+ * Any value outside 1..9 means auto.  sfod_last_conv_kernel names the kernel a launch ran.  For A/B runs and parity tests. */
 int sfod_set_conv3x3_variant(int variant);
+/* the kernel instantiation the calling thread's last convolution launch ran (halo-patch forward / data gradient, generic
+ * implicit GEMM incl. split-K, halo-patch and generic weight gradient), e.g. "k_conv3x3_m16<8,2,1,0,0,1>": copied into buf
+ * (NUL-terminated, truncated to n - 1 characters); returns the full length, 0 if nothing was launched yet, -1000 for a NULL
+ * buf or n <= 0.  A host-side record set where the launch is issued; it says which code ran, not whether it finished. */
+int sfod_last_conv_kernel(char* buf, int n);
 /* Deterministic gradients (default 0; environment SFOD_DETERMINISTIC, config SFOD.DETERMINISTIC): the generic weight-gradient
  * kernels (1x1 / linear / first layer / fp32) store every pixel split's partial tile into a slab of the workspace
  * (sfod_conv_wgrad_ws_bytes grows accordingly) and sum the slabs in split order instead of combining them with float atomics,

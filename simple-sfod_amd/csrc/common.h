@@ -10,6 +10,17 @@
 
 void sfod_set_error(const char* fmt, ...);
 
+// Host-only record of the convolution kernel instantiation the calling thread launched last (sfod_last_conv_kernel).  The
+// launchers set it right where they launch, so it names what ran, not what a planner predicted.  `name` must live as long
+// as the process: a string literal or a launcher's function-local static (sfod_kernel_name).  Every conv entry point clears
+// it first (sfod_note_conv_kernel(nullptr)), so a launch path that records nothing cannot leave an earlier call's name.
+// sfod_note_conv_kernel_then appends a second launch of the same call (reported as "first+then").
+void sfod_note_conv_kernel(const char* name);
+void sfod_note_conv_kernel_then(const char* name);
+#include <string>
+std::string sfod_kernel_name(const char* fmt, ...);
+template <typename T> static inline const char* sfod_type_name() { return sizeof(T) == 4 ? "float" : "bf16_t"; }
+
 static inline int sfod_check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

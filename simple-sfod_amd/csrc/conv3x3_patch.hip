@@ -1292,7 +1292,7 @@ k_conv3x3_m16(P3Args a) {
 //      (SFOD_P3_M16=0 / sfod_set_conv3x3_m16(0): the 32x32x16 kernel everywhere, for A/B runs)
 //   6  the same on 4 waves per workgroup (k_conv3x3_m16<4, 8>, wave tile 128 x 64)
 //   7  shape 3 on v_mfma_f32_16x16x32 (round 6: k_conv3x3_m16<4, 4, NWN = 1>: 4 waves x (64 px x 64 ch), 64 KiB, two workgroups
-//      per CU; operand pairs with Cin % 32 == 0).  Slower than shape 3 on every layer measured (see sfod_p3_launch): never the
+//      per CU; operand pairs with physical Cin % 64 == 0, as 7 / 8 / 9 all).  Slower than shape 3 on every layer measured (see sfod_p3_launch): never the
 //      automatic choice unless SFOD_P3_M16_N64=1
 //   8  shape 4 on it (k_conv3x3_m16<8, 4, NWN = 1>: 512 px x 64 ch, 96 KiB, one workgroup per CU)
 //   9  shape 3 on it with 8 waves x (32 px x 64 ch) (k_conv3x3_m16<8, 2, NWN = 1>: 64 KiB, two workgroups = 16 waves per CU)
@@ -1301,7 +1301,8 @@ k_conv3x3_m16(P3Args a) {
 // L2 -> LDS traffic on every VGG shape; between the two small shapes the 64 x 64 wave tile needs one LDS
 // fragment read per MFMA instead of 1.5 (the 32 x 64 tile keeps the LDS array ~100 % busy at full MFMA rate)
 // and wins by 7-18 % wherever its 128-channel tiles still fill the chip (>= 512 workgroups).
-// SFOD_P3_VARIANT=1..4 / sfod_set_conv3x3_variant force a shape where the channel counts allow it (A/B, tests).
+// SFOD_P3_VARIANT=1..9 / sfod_set_conv3x3_variant force a shape where the channel counts allow it (A/B, tests): 3 / 4 / 7 /
+// 8 / 9 need physical Cin % 64 == 0, 5..9 operand pairs; elsewhere another kernel runs (sfod_last_conv_kernel names it).
 // process-wide tuning knob for A/B runs and tests (relaxed atomic: a plain word, no ordering needed); -1: not
 // initialised (SFOD_P3_VARIANT or 0 = auto).  It selects among kernels that compute the same values.
 static std::atomic<int> g_p3_variant{-1};
@@ -1422,6 +1423,9 @@ static int p3_launch_m16(P3Args a, hipStream_t s) {
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
   if (attr_rc != hipSuccess) { sfod_set_error("hipFuncSetAttribute(m16): %s", hipGetErrorString(attr_rc)); return -(int)attr_rc; }
   a.nbody = a.Cin / 64;
+  static const std::string kname =
+      sfod_kernel_name("k_conv3x3_m16<%d,%d,%d,%d,%d,%d>", NW, NIP, FMT, (int)RED, (int)XF, NWN);
+  sfod_note_conv_kernel(kname.c_str());
   hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(NW * 64), LDS, s, a);
   return sfod_check_launch("conv3x3_m16");
 }
@@ -1434,6 +1438,9 @@ static int p3_launch_one(const P3Args& a, hipStream_t s) {
   static const hipError_t attr_rc =
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
   if (attr_rc != hipSuccess) { sfod_set_error("hipFuncSetAttribute(p3): %s", hipGetErrorString(attr_rc)); return -(int)attr_rc; }
+  static const std::string kname =
+      sfod_kernel_name("k_conv3x3_patch<%d,%d,%s,%d,%d>", G, FM, sfod_type_name<OutT>(), SPLIT, (int)RED);
+  sfod_note_conv_kernel(kname.c_str());
   hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(512), LDS, s, a);
   return sfod_check_launch("conv3x3_patch");
 }

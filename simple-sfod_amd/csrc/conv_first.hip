@@ -451,6 +451,7 @@ int sfod_f1_launch(const void* x, const void* w, const float* bias, void* y, flo
   a.ntiles = B * a.tiles_y * a.tiles_x;
   const int resident = split ? 256 * 3 : 256 * 8;      // bf16x3: 3 workgroups per CU (LDS), each stages the weights once
   int grid = a.ntiles < resident ? a.ntiles : resident;
+  sfod_note_conv_kernel(split == 2 ? "k_conv_first_x3<2>" : (split ? "k_conv_first_x3<1>" : "k_conv_first"));
   if (split == 2) hipLaunchKernelGGL(k_conv_first_x3<2>, dim3(grid), dim3(256), 0, s, a);
   else if (split) hipLaunchKernelGGL(k_conv_first_x3<1>, dim3(grid), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_conv_first, dim3(grid), dim3(256), 0, s, a);

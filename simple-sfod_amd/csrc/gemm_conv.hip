@@ -572,6 +572,9 @@ static int launch_one(const void* x, const void* w, const float* bias, void* y, 
   if (attr_rc != hipSuccess) { sfod_set_error("hipFuncSetAttribute: %s", hipGetErrorString(attr_rc)); return -(int)attr_rc; }
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.Cout + BN - 1) / BN;
   const int nt = tiles_m * tiles_n;
+  static const std::string kname = sfod_kernel_name("k_conv_fwd<%s,%s,2,%d,%d,%d,%d,%d,%d>", sfod_type_name<T>(),
+                                                    sfod_type_name<OutT>(), WN, (int)UT, WR, NST, SPLIT, BKB);
+  sfod_note_conv_kernel(kname.c_str());
   hipLaunchKernelGGL(kern, dim3(nt, a.kt_per ? a.nsplit : 1), dim3(WR * 128), LDS, s, (const T*)x, (const T*)w, bias, (OutT*)y,
                      stats, a, tiles_n, nt);
   return sfod_check_launch("conv_fwd");
@@ -629,6 +632,7 @@ static int launch_splitk(const void* x, const void* w, const float* bias, float*
   if (rc != 0) return rc;
   const int64_t total = (int64_t)a.M * (a.Cout / 4);
   const int grid = (int)std::min<int64_t>((total + 255) / 256, 2048);
+  sfod_note_conv_kernel_then("k_splitk_sum");      // behind the partial-tile kernel launch_one recorded
   hipLaunchKernelGGL(k_splitk_sum, dim3(grid), dim3(256), 0, s, ws, a.nsplit, a.slab, a.M, a.Cout, bias, act, y, ldy);
   return sfod_check_launch("splitk_sum");
 }
@@ -746,6 +750,7 @@ extern "C" int sfod_conv_first_fused(const void* x, const void* w, const float* 
 extern "C" int sfod_conv_first_fused_ws(const void* x, const void* w, const uint32_t* w_absmax, const float* bias,
                                         const float* scale, const float* shift, void* y, float* stats, int B, int H,
                                         int W, int ldy, int act, int dt, void* stream) {
+  sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE(conv_shape_fits(B, H, W, 8, 64, 3) && sfod_ints_ok({ldy}), "conv_first_fused: negative or oversized extent");
   SFOD_REQUIRE(x != nullptr && w != nullptr, "conv_first_fused: null operand");
   SFOD_REQUIRE(w_absmax == nullptr || dt == SFOD_F16X3, "conv_first: scaled weights are an SFOD_F16X3 format");
@@ -790,6 +795,7 @@ extern "C" int64_t sfod_conv_fwd_scratch_bytes(int B, int H, int W, int Cin, int
 extern "C" int sfod_conv_fwd_scratch(const void* x, const void* w, const uint32_t* w_absmax, const float* bias, void* y,
                                      int B, int H, int W, int Cin, int Cout, int ksize, int ldy, int act, float* stats,
                                      int dt, int out_dt, void* scratch, int64_t scratch_bytes, void* stream) {
+  sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE(conv_shape_fits(B, H, W, Cin, Cout, ksize) && sfod_ints_ok({ldy}) && sfod_i64s_ok({scratch_bytes}),
                "conv_fwd: negative or oversized extent");
   SFOD_REQUIRE(x != nullptr && w != nullptr && y != nullptr, "conv_fwd: null operand (x, w, y)");
@@ -859,6 +865,7 @@ extern "C" int sfod_conv_fwd_bnin_supported(int B, int H, int W, int Cin, int Co
 extern "C" int sfod_conv_fwd_bnin(const float* x_pre, const float* in_mean, const float* in_invstd, const float* in_gamma,
                                   const float* in_beta, const void* w, const float* bias, float* y, int B, int H, int W,
                                   int Cin, int Cout, int ldy, int act, float* stats, int dt, void* stream) {
+  sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE(conv_shape_fits(B, H, W, Cin, Cout, 3) && sfod_ints_ok({ldy}), "conv_fwd_bnin: negative or oversized extent");
   SFOD_REQUIRE(sfod_conv_fwd_bnin_supported(B, H, W, Cin, Cout, dt), "conv_fwd_bnin: shape not served (sfod_conv_fwd_bnin_supported)");
   SFOD_REQUIRE(x_pre && in_mean && in_invstd && in_gamma && in_beta && w && y, "conv_fwd_bnin: null argument");
@@ -886,6 +893,7 @@ extern "C" int sfod_conv_dgrad_bnred_blocks(int B, int H, int W, int Cin, int Co
 extern "C" int sfod_conv_dgrad_bnred(const void* x, const void* w, void* dz, int B, int H, int W, int Cin, int Cout,
                                      int dt, const float* y, const float* mean, const float* invstd,
                                      const float* gamma, const float* beta, float* red_ws, void* stream) {
+  sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE(conv_shape_fits(B, H, W, Cin, Cout, 3), "conv_dgrad_bnred: negative or oversized extent");
   SFOD_REQUIRE(x != nullptr && w != nullptr && dz != nullptr, "conv_dgrad_bnred: null operand");
   SFOD_REQUIRE(sfod_conv_dgrad_bnred_blocks(B, H, W, Cin, Cout, dt) > 0,
@@ -1504,6 +1512,7 @@ extern "C" int sfod_conv_wgrad_oihw_supported(int B, int H, int W, int Cin, int 
 extern "C" int sfod_conv_wgrad_oihw(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin,
                                     int Cout, int ksize, int lddy, int dt, int accumulate, void* ws,
                                     int64_t ws_bytes, void* stream) {
+  sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE(conv_shape_fits(B, H, W, Cin, Cout, ksize) && sfod_ints_ok({lddy}) && sfod_i64s_ok({ws_bytes}),
                "conv_wgrad_oihw: negative or oversized extent");
   SFOD_REQUIRE(x != nullptr && dy != nullptr && dw_oihw != nullptr, "conv_wgrad_oihw: null operand");
@@ -1518,6 +1527,7 @@ extern "C" int sfod_conv_wgrad_oihw(const void* x, const void* dy, float* dw_oih
 extern "C" int sfod_conv_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int Cin,
                                int Cout, int ksize, int lddy, int dt, void* ws, int64_t ws_bytes,
                                void* stream) {
+  sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE(conv_shape_fits(B, H, W, Cin, Cout, ksize) && sfod_ints_ok({lddy}) && sfod_i64s_ok({ws_bytes}),
                "conv_wgrad: negative or oversized extent");
   SFOD_REQUIRE(x != nullptr && dy != nullptr && dw != nullptr, "conv_wgrad: null operand");
@@ -1569,10 +1579,13 @@ extern "C" int sfod_conv_wgrad(const void* x, const void* dy, float* dw, int B, 
     static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_wgrad_x3w),
                                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     SFOD_REQUIRE(attr_rc == hipSuccess, "wgrad: cannot raise the dynamic LDS limit");
+    sfod_note_conv_kernel("k_conv_wgrad_x3w");
     hipLaunchKernelGGL(k_conv_wgrad_x3w, dim3(tiles * g.splits), dim3(512), LDS, s, (const bf16_t*)x, (const bf16_t*)dy,
                        dw_out, a);
   } else {
     dim3 grid(tiles * g.splits);
+    sfod_note_conv_kernel(dt == SFOD_F32 ? "k_conv_wgrad<float,2,2,0>"
+                                         : (split ? "k_conv_wgrad<bf16_t,2,2,1>" : "k_conv_wgrad<bf16_t,2,2,0>"));
     if (dt == SFOD_F32)
       hipLaunchKernelGGL((k_conv_wgrad<float, 2, 2>), grid, dim3(256), 2 * 2 * 32 * 512, s, (const float*)x,
                          (const float*)dy, dw_out, a);

@@ -166,6 +166,7 @@ extern "C" int sfod_stem7x7_supported(int B, int H, int W, int Cp, int dt) {
 
 extern "C" int sfod_stem7x7(const float* x, const void* w_packed, const uint32_t* w_absmax, const float* bias, float* y,
                             int B, int H, int W, int Cp, int act, int dt, void* stream) {
+  sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE_EXTENTS("stem7x7", B, H, W, Cp);
   SFOD_REQUIRE(sfod_stem7x7_supported(B, H, W, Cp, dt), "stem7x7: operand pairs (SFOD_BF16X3 / SFOD_F16X3), Cp a multiple of 4, non-empty input");
   SFOD_REQUIRE(x != nullptr && w_packed != nullptr && y != nullptr, "stem7x7: null argument (x, w_packed, y)");
@@ -177,6 +178,7 @@ extern "C" int sfod_stem7x7(const float* x, const void* w_packed, const uint32_t
   const int ntiles = B * tiles_x * tiles_y;
   hipStream_t s = (hipStream_t)stream;
   const int grid = ntiles < 256 * 3 ? ntiles : 256 * 3;               // persistent: three workgroups per CU share the LDS
+  sfod_note_conv_kernel(dt == SFOD_F16X3 ? "k_stem7x7<2>" : "k_stem7x7<1>");
   if (dt == SFOD_F16X3) {
     static const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stem7x7<2>),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);

@@ -286,13 +286,26 @@ def set_wgrad3x3_pipe(on):
 
 
 def set_gemm_tile(tile):
-    """Tile shape of the generic implicit-GEMM kernel: 0 the planner's choice, 1..10 see include/sfod_hip.h (A/B runs, tests)."""
+    """Tile shape of the generic implicit-GEMM kernel: 0 the planner's choice, 1..8 see include/sfod_hip.h (A/B runs, tests;
+    other values mean 0).  A shape the layer cannot take falls back to the planner's: ``last_conv_kernel`` says what ran."""
     load().sfod_set_gemm_tile(int(tile))
 
 
 def set_conv3x3_variant(variant):
-    """Workgroup shape of the halo-patch kernel: 0 auto, 1..5 see include/sfod_hip.h (A/B runs, tests)."""
+    """Workgroup shape of the halo-patch kernel: 0 auto, 1..9 see include/sfod_hip.h (A/B runs, tests; other values mean 0).
+    7 / 8 / 9 need operand pairs with logical Cin % 32 == 0; elsewhere they run another kernel: ``last_conv_kernel`` says
+    which."""
     load().sfod_set_conv3x3_variant(int(variant))
+
+
+def last_conv_kernel():
+    """Name of the kernel instantiation the calling thread's last convolution launch ran (e.g. "k_conv3x3_m16<8,2,1,0,0,1>"),
+    "" before the first one: a host-side record set where the launch is issued (include/sfod_hip.h sfod_last_conv_kernel)."""
+    buf = ctypes.create_string_buffer(256)
+    n = load().sfod_last_conv_kernel(buf, len(buf))
+    if n < 0:
+        _chk(n, "sfod_last_conv_kernel")
+    return buf.value.decode()
 
 
 def set_deterministic(on):

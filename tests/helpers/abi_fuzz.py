@@ -173,6 +173,10 @@ def main():
     # (param, grad, mom, teacher, n, lr, momentum, weight_decay, grad_scale, ema_keep, ema_one_minus_keep, first_step, stream)
     sgd = [P, P, P, None, 1000, P, 0.9, 1e-4, 1.0, 0.9996, 0.0004, 0, None]
     expect_badarg("sfod_sgd_ema", sgd, [("n", -4), ("param", None), ("grad", None), ("mom", None), ("lr", None)])
+    # (buf, n): the kernel record refuses a NULL buffer and n <= 0 (a valid call answers the name's length, >= 0)
+    expect_badarg("sfod_last_conv_kernel", [P, 64], [("buf", None), ("n", 0), ("n", -1), ("n", -2 ** 31)])
+    rc = lib.sfod_last_conv_kernel(P, 64)
+    contract.append({"fn": "sfod_last_conv_kernel", "arg": "valid", "value": 64, "rc": rc, "ok": rc >= 0, "msg": ""})
     n_contract_bad = sum(not c["ok"] for c in contract)
     print(json.dumps({"entry_points": len(protos), "random_calls": calls, "random_violations": bad,
                       "violations": {k: [str(x)[:300] for x in v[:5]] for k, v in outcomes.items()},

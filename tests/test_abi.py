@@ -61,6 +61,19 @@ def test_launch_planners_answer_without_a_gpu(sfod):
     assert lib.sfod_last_error() == b""
 
 
+def test_last_conv_kernel_record(sfod):
+    """sfod_last_conv_kernel: a host-side string (no device needed); NULL buffer and n <= 0 are refused with a message, a
+    short buffer gets a truncated, NUL-terminated copy and the full length."""
+    import ctypes
+    lib = sfod.native.load()
+    assert isinstance(sfod.native.last_conv_kernel(), str)
+    for buf, n in ((None, 16), (ctypes.create_string_buffer(4), 0), (ctypes.create_string_buffer(4), -1)):
+        assert lib.sfod_last_conv_kernel(buf, n) == -1000 and lib.sfod_last_error()
+    buf = ctypes.create_string_buffer(b"xxxx", 4)
+    n = lib.sfod_last_conv_kernel(buf, 1)
+    assert n >= 0 and buf.raw[0] == 0
+
+
 def test_c_abi_host_side_survives_hostile_arguments_under_asan_and_ubsan(sfod, tmp_path):
     """The library's HOST code (argument validation, launch planners, ``*_supported`` / ``*_bytes`` / ``*_blocks`` queries)
     built with -fsanitize=address,undefined and no device code (csrc/build.py::build_host_sanitized), fuzzed by

@@ -12,6 +12,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import definition_check as dc
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 TOL = 3e-5
@@ -42,6 +44,12 @@ def split_ref(x):
 
 def to_split(native, x_dev):
     return native.cast(x_dev.contiguous(), native.SPLIT_DTYPE)
+
+
+def ran_forced(native, wg, cin):
+    """A forced workgroup shape ran the kernel it names -- or, where the channel count does not allow it, the documented one."""
+    if wg:
+        assert native.last_conv_kernel() == dc.expected_patch_kernel(wg, 2 * cin, 1), native.last_conv_kernel()
 
 
 def conv_ref64(x, w, bias=None, padding=0):
@@ -126,9 +134,11 @@ def test_conv3x3_patch_kernel(native, shape, variant, wg):
         assert native.query("sfod_conv_fwd_algo", B, H, W, Cin, Cout, 3, native.BF16X3) == 2
         if variant == "plain":
             y = native.conv_fwd(xd, wp, bias.to(DEV), Cout, 3)
+            ran_forced(native, wg, Cin)
             assert rel_err(nchw(y.cpu()), ref) < TOL
         elif variant == "relu_stats":
             y, stats = native.conv_fwd(xd, wp, bias.to(DEV), Cout, 3, act=1, want_stats=True)
+            ran_forced(native, wg, Cin)
             assert rel_err(nchw(y.cpu()), F.relu(ref)) < TOL
             rm, rv = torch.zeros(Cout, device=DEV), torch.ones(Cout, device=DEV)
             mean, invstd = native.bn_finalize(stats, B * H * W, Cout, rm, rv, 0.1, 1e-5)
@@ -137,6 +147,7 @@ def test_conv3x3_patch_kernel(native, shape, variant, wg):
                                        rtol=1e-4, atol=1e-5)
         else:
             y = native.conv_fwd(xd, wp, None, Cout, 3, ldy=Cout + 8)
+            ran_forced(native, wg, Cin)
             assert rel_err(nchw(y[..., :Cout].cpu()), ref - bias.double().view(1, -1, 1, 1)) < TOL
             assert (y[..., Cout:] == 0).all()
     finally:
@@ -210,6 +221,9 @@ def test_conv3x3_patch_wgrad(native, shape, pipe):
         native.set_conv_algo(2)
         assert native.query("sfod_conv_wgrad_ws_bytes", B, H, W, Cin, Cout, 3, Cout, native.BF16X3) >= 16 * Cout * 9 * Cin
         dwp = native.conv_wgrad(xd, dyd, Cout, 3)
+        ran = {2: "k_wgrad3x3_w64" if Cin >= 64 else "k_wgrad3x3_patch<4,1,1>", 1: "k_wgrad3x3_patch<4,1,1>",
+               0: "k_wgrad3x3_patch<4,1,0>"}[pipe]
+        assert native.last_conv_kernel() == ran, native.last_conv_kernel()
         dwp2 = native.conv_wgrad(xd, dyd, Cout, 3)
         assert native.conv_wgrad_oihw_supported(xd, dyd, Cout, 3)
         direct = torch.full((Cout, Cin, 3, 3), float("nan"), dtype=torch.float32, device=DEV)
@@ -374,8 +388,10 @@ def test_conv3x3_pairs_under_load_is_deterministic(native, wg):
         native.set_conv_algo(2)
         native.set_conv3x3_variant(2)
         ref, ref_stats = native.conv_fwd(x, w, bias, Cout, 3, want_stats=True)
+        ran_forced(native, 2, Cin)
         native.set_conv3x3_variant(wg)
         outs = [native.conv_fwd(x, w, bias, Cout, 3, want_stats=True) for _ in range(6)]
+        ran_forced(native, wg, Cin)     # the kernel under test, not a fallback: Cin = 256 takes every shape
         torch.cuda.synchronize()
     finally:
         native.set_conv_algo(0)
@@ -411,7 +427,14 @@ def test_dgrad_with_fused_batchnorm_backward_reduction(native, shape, variant):
         served = native.query("sfod_conv_dgrad_bnred_blocks", B, H, W, Cup, C, native.BF16X3) > 0
         assert served or variant != 0 or shape == (1, 33, 31, 64, 64)
         dz_ref = native.conv_fwd(dys, wr, None, C, 3)
+        if variant:     # the forced shape ran, or -- where the planner keeps this layer off the halo-patch kernel -- the generic one
+            if native.query("sfod_conv_fwd_algo", B, H, W, Cup, C, 3, native.BF16X3) == 2:
+                assert native.last_conv_kernel() == dc.expected_patch_kernel(variant, 2 * Cup, 1), native.last_conv_kernel()
+            else:
+                assert native.last_conv_kernel().startswith("k_conv_fwd<bf16_t,float,2,"), native.last_conv_kernel()
         fused = native.conv_dgrad_bnred(dys, wr, C, yd, mean, invstd, gd, bd)
+        if fused is not None and variant:      # the same shape with the BatchNorm-backward epilogue
+            assert native.last_conv_kernel() == dc.expected_patch_kernel(variant, 2 * Cup, 1, red=True), native.last_conv_kernel()
     finally:
         native.set_conv3x3_variant(0)
     if not served:
@@ -615,6 +638,9 @@ def test_gemm_tiles_with_64_byte_stages_equal_the_planners_choice(native, shape,
         y0, st0 = native.conv_fwd(xd, wp, bias.to(DEV), N, 1, act=1, want_stats=True)
         native.set_gemm_tile(tile)
         y1, st1 = native.conv_fwd(xd, wp, bias.to(DEV), N, 1, act=1, want_stats=True)
+        wn, wr, nst = {6: (2, 4, 3), 7: (2, 2, 3), 8: (2, 4, 4)}[tile]
+        split = 1 if fmt == "bf16x3" else 2
+        assert native.last_conv_kernel() == f"k_conv_fwd<bf16_t,float,2,{wn},1,{wr},{nst},{split},64>", native.last_conv_kernel()
         torch.cuda.synchronize()
     finally:
         native.set_gemm_tile(0)

@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import definition_check as dc
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 TOL = 1e-6
@@ -46,6 +48,12 @@ def splith_ref(x):
 
 def to_pairs(native, x_dev):
     return native.cast(x_dev.contiguous(), native.SPLITH_DTYPE)
+
+
+def ran_forced(native, wg, cin):
+    """A forced workgroup shape ran the kernel it names -- or, where the channel count does not allow it, the documented one."""
+    if wg:
+        assert native.last_conv_kernel() == dc.expected_patch_kernel(wg, 2 * cin, 2), native.last_conv_kernel()
 
 
 def conv_ref64(x, w, bias=None, padding=0):
@@ -175,9 +183,11 @@ def test_conv3x3_patch_kernel(native, shape, variant, wg):
         assert native.query("sfod_conv_fwd_algo", B, H, W, Cin, Cout, 3, native.F16X3) == 2
         if variant == "plain":
             y = native.conv_fwd(xd, wp, bias.to(DEV), Cout, 3)
+            ran_forced(native, wg, Cin)
             assert rel_err(nchw(y.cpu()), ref) < TOL
         elif variant == "relu_stats":
             y, stats = native.conv_fwd(xd, wp, bias.to(DEV), Cout, 3, act=1, want_stats=True)
+            ran_forced(native, wg, Cin)
             assert rel_err(nchw(y.cpu()), F.relu(ref)) < TOL
             rm, rv = torch.zeros(Cout, device=DEV), torch.ones(Cout, device=DEV)
             mean, invstd = native.bn_finalize(stats, B * H * W, Cout, rm, rv, 0.1, 1e-5)
@@ -186,6 +196,7 @@ def test_conv3x3_patch_kernel(native, shape, variant, wg):
                                        rtol=1e-4, atol=1e-5)
         else:
             y = native.conv_fwd(xd, wp, None, Cout, 3, ldy=Cout + 8)
+            ran_forced(native, wg, Cin)
             assert rel_err(nchw(y[..., :Cout].cpu()), ref - bias.double().view(1, -1, 1, 1)) < TOL
             assert (y[..., Cout:] == 0).all()
     finally:
@@ -428,3 +439,5 @@ def test_kernels_compute_the_product_they_are_defined_to_compute(native, fmt, sh
     assert e_def < 2.5e-7 * math.sqrt(K / 256.0), (e_def, e_exact)      # fp32 accumulation: ~1.1e-8 * sqrt(K) (seen 1.8e-7 / 3.5e-7 / 7.7e-7)
     if fmt == "bf16":
         assert e_def < 0.2 * e_exact        # the bf16-pair mode's error IS its definition's, not the kernel's
+    # and per element (tests/helpers/definition_check.py): no tile, row or column of the output may depart from the definition
+    dc.assert_matches_definition(y, defined, sp.magnitude_linear(x, w), K, fmt + "x3", layout="rows", label=f"linear {shape}")

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import definition_check as dc
 from oracle import box_ops as OB
 from oracle import model as om
 from oracle.roi_align import roi_align as oracle_roi_align
@@ -76,6 +77,12 @@ def test_conv_fwd(native, dtype, shape, act):
     assert rel_err(got, ref) < tol
 
 
+def ran_forced(native, wg, cin, out=None):
+    """A forced workgroup shape ran the kernel it names -- or, where the channel count does not allow it, the documented one."""
+    if wg:
+        assert native.last_conv_kernel() == dc.expected_patch_kernel(wg, cin, 0, out), native.last_conv_kernel()
+
+
 @pytest.mark.parametrize("shape", [
     # B, H, W, Cin, Cout  -- halo-patch kernel: tile overhang, N tails, both workgroup shapes
     (2, 37, 75, 64, 128),     # G=1, 2 body iterations
@@ -104,6 +111,7 @@ def test_conv3x3_patch_kernel(native, shape, variant, wg):
         assert native.query("sfod_conv_stats_blocks", B, H, W, Cin, Cout, 3, native.BF16) < (B * H * W + 127) // 128 + B * 64
         if variant == "plain":
             y = native.conv_fwd(xd, wp, bias.to(DEV), Cout, 3)
+            ran_forced(native, wg, Cin)
             assert rel_err(nchw(y.float().cpu()), ref) < 6e-3
             if Cin & (Cin - 1) == 0:  # the generic kernel needs a power-of-two channel count
                 native.set_conv_algo(1)
@@ -112,6 +120,7 @@ def test_conv3x3_patch_kernel(native, shape, variant, wg):
                 assert rel_err(y.float().cpu(), y_gen.float().cpu()) < 4e-3
         elif variant == "relu_stats":
             y, stats = native.conv_fwd(xd, wp, bias.to(DEV), Cout, 3, act=1, want_stats=True)
+            ran_forced(native, wg, Cin)
             assert rel_err(nchw(y.float().cpu()), F.relu(ref)) < 6e-3
             rm, rv = torch.zeros(Cout, device=DEV), torch.ones(Cout, device=DEV)
             mean, invstd = native.bn_finalize(stats, B * H * W, Cout, rm, rv, 0.1, 1e-5)
@@ -121,6 +130,7 @@ def test_conv3x3_patch_kernel(native, shape, variant, wg):
             torch.testing.assert_close(invstd.cpu(), torch.rsqrt(v_ref + 1e-5), rtol=3e-3, atol=1e-4)
         else:
             y = native.conv_fwd(xd, wp, None, Cout, 3, out_dtype=torch.float32, ldy=Cout + 8)
+            ran_forced(native, wg, Cin, out="float")
             assert y.shape[-1] == Cout + 8
             assert rel_err(nchw(y[..., :Cout].cpu()), ref - bias.view(1, -1, 1, 1)) < 2e-3
             assert (y[..., Cout:] == 0).all()
@@ -146,6 +156,7 @@ def test_conv3x3_patch_under_load_is_deterministic(native, wg):
         native.set_conv_algo(2)
         native.set_conv3x3_variant(wg)
         ys = [native.conv_fwd(x, w, bias, Cout, 3, want_stats=True)[0] for _ in range(6)]
+        ran_forced(native, wg, Cin)     # the shape under test, not a fallback: Cin = 256 takes every shape
         torch.cuda.synchronize()
     finally:
         native.set_conv_algo(0)

@@ -380,6 +380,40 @@ def test_split_precision_definitions_and_their_own_error():
     e_h_unscaled = err(xh @ wh.t() + xh @ wl.t() + xl @ wh.t())
     assert 2e-6 < e_bf < 8e-6 and e_h < 2e-7 and e_h < e_bf / 20, (e_bf, e_h)
     assert e_h_unscaled > 2.5 * e_h, (e_h_unscaled, e_h)
+    # every mode through the generic helpers: linear_mode of the pair modes IS linear(); the plain modes are exact products
+    for mode, fmt in sp.PAIR_FORMAT.items():
+        assert torch.equal(sp.linear_mode(x, w, mode), sp.linear(x, w, fmt))
+    assert torch.equal(sp.linear_mode(x, w, "fp32"), exact)
+    assert torch.equal(sp.linear_mode(x, w, "bf16"), x.bfloat16().double() @ w.bfloat16().double().t())
+    # the convolution definitions equal linear() on the unfolded (im2col) operands, for every mode, stride and padding
+    xc = torch.randn(2, 24, 9, 11, generator=g) + 0.3
+    wc = torch.randn(40, 24, 3, 3, generator=g) / 15
+    for mode in sp.MODES:
+        for pad, stride in ((1, 1), (0, 1), (3, 2)):
+            y = sp.conv2d(xc, wc, mode, padding=pad, stride=stride)
+            cols = torch.nn.functional.unfold(xc, 3, padding=pad, stride=stride)           # [B, Cin * 9, L]
+            flat = cols.transpose(1, 2).reshape(-1, 24 * 9)
+            ref = sp.linear_mode(flat, wc.reshape(40, -1), mode).reshape(2, -1, 40).transpose(1, 2).reshape(y.shape)
+            torch.testing.assert_close(y, ref, rtol=1e-13, atol=1e-13)
+            mag = sp.magnitude(xc, wc, padding=pad, stride=stride)
+            assert (mag * (1 + 2.0 ** -7) >= y.abs()).all()          # (bf16 operands: within their own rounding)
+        # the weight gradient: d/dw of <conv2d(x, w), dy> summed over the same split pairs (f16x3: bf16 pairs)
+        dy = torch.randn(2, 40, 9, 11, generator=g) * 1e-3
+        dw = sp.conv2d_wgrad(xc, dy, wc.shape, mode)
+        cols = torch.nn.functional.unfold(xc, 3, padding=1).transpose(1, 2).reshape(-1, 24 * 9)
+        dyr = dy.permute(0, 2, 3, 1).reshape(-1, 40)
+        ref = sp.linear_mode(dyr.t().contiguous(), cols.t().contiguous(), "bf16x3" if mode == "f16x3" else mode)
+        torch.testing.assert_close(dw.reshape(40, -1), ref, rtol=1e-12, atol=1e-18)
+        assert (sp.magnitude_wgrad(xc, dy, wc.shape) * (1 + 2.0 ** -7) >= dw.abs()).all()
+    # the data gradient through rot180 weights is the adjoint of the forward convolution
+    dy = torch.randn(2, 40, 9, 11, generator=g, dtype=torch.float64)
+    dx = torch.nn.functional.conv2d(dy, sp.rot180(wc.double()), padding=1)
+    xr = torch.randn(2, 24, 9, 11, generator=g, dtype=torch.float64)
+    lhs = (torch.nn.functional.conv2d(xr, wc.double(), padding=1) * dy).sum()
+    assert abs(float(lhs - (xr * dx).sum())) < 1e-9 * float(lhs.abs() + 1)
+    # f16x3 forward weights stay under their scale: the definition divides it back out exactly
+    hs, s = sp.terms(xc, wc, "f16x3", scale_b=True)
+    assert s == sp.weight_scale(wc) and 2.0 ** 13 <= float((hs[0][1] + hs[1][1]).abs().max()) < 2.0 ** 14 + 1
 
 
 def test_teacher_pass_defers_batchnorm_only_where_it_pays(sfod, monkeypatch):
