@@ -243,7 +243,9 @@ int sfod_pack_fc_weight_ld_ws(const float* w, void* out, uint32_t* absmax, int N
                               int ld, int dt, void* stream);
 int sfod_unpack_fc_wgrad_ld(const float* dw_packed, float* dw, int N, int K, int chw_c, int ld,
                             int accumulate, void* stream);
-/* column sums of a [M, ld] matrix's first N columns: bias gradients.  db[n] (+)= sum_m dy[m][n] */
+/* column sums of a [M, ld] matrix's first N columns: bias gradients.  db[n] (+)= sum_m dy[m][n].  Held per column to the
+ * fp64 sum within 8 sqrt(M) 2^-24 sum_m |dy[m][n]| (+ 2^-24 |db| when accumulating), in the sliced and the deterministic form
+ * (tests/test_gpu_pointwise_definition.py); columns [N, ld) are never read. */
 int sfod_bias_grad(const void* dy, float* db, int M, int N, int ld, int accumulate, int dt,
                    void* stream);
 
@@ -266,7 +268,14 @@ int sfod_set_bn_finalize_fused(int on);
 /* size (in floats, 8-byte aligned) of the `ws` scratch of sfod_bn_finalize */
 int sfod_bn_finalize_ws_floats(int C);
 /* z = relu(gamma*(y-mean)*invstd+beta); `pool` is a flag word: bit 0 additionally 2x2/2 max-pools z
- * (floor), bit 1 drops the ReLU (d2 BottleneckBlock conv3 / shortcut norms, no activation) */
+ * (floor: H / 2 by W / 2, the last row / column of an odd map is not covered), bit 1 drops the ReLU (d2 BottleneckBlock
+ * conv3 / shortcut norms, no activation).
+ * Definition the kernels are held to, per element (oracle/pointwise_definitions.py bn_affine,
+ * tests/test_gpu_pointwise_definition.py): z_pre = (y - mean) * (invstd * gamma) + beta (+ residual) within 5 * 2^-24 of
+ * (|y| + |mean|) |invstd gamma| + |beta| (+ |residual|), then the output rounding -- for every output type, the pair outputs
+ * included.  The ReLU is fmaxf(z_pre, 0): a NaN gives +0 (it is NOT propagated, unlike torch.relu), -0 gives +0; the window
+ * maximum drops a NaN the same way (identity 0 with the ReLU, -inf without).  sfod_bn_add_relu_fwd and sfod_add_act share
+ * this, and the backward gates (z_pre > 0, y > 0) pass no gradient there. */
 int sfod_bn_relu_pool_fwd(const void* y, const float* mean, const float* invstd,
                           const float* gamma, const float* beta, void* z, int B, int H, int W,
                           int C, int pool, int dt, int out_dt, void* stream);
@@ -286,6 +295,12 @@ int sfod_bn_add_relu_fwd(const void* y, const float* mean, const float* invstd, 
                          int C, int dt, int pairs_dt, void* stream);
 /* backward of the block above.  dz: grad w.r.t. block output; y: saved conv output; returns dy
  * (grad w.r.t. conv output), dgamma, dbeta.  ws: fp32 workspace [nblk*2*C] (see ws query).
+ * Definition (oracle/pointwise_definitions.py bn_backward; held per channel / per element by
+ * tests/test_gpu_pointwise_definition.py): g = dz routed to the FIRST maximum of z_pre in its 2x2 window in the order (0,0),
+ * (0,1), (1,0), (1,1) -- an exact tie sends the whole gradient to the earlier member -- gated by z_pre > 0 unless bit 1 of
+ * `pool`; dbeta = sum g, dgamma = sum g * xhat, dy = gamma * invstd * (g - dbeta / M - xhat * dgamma / M) with
+ * xhat = (y - mean) * invstd and M = B * H * W: the leftover pixels of an odd H / W count in M, their g is 0 and their dy is
+ * the mean terms alone.  A pooled map without any window (H or W = 1) has an empty dz (may be NULL): dgamma = dbeta = 0.
  * dgamma_acc / dbeta_acc (may be NULL): the parameters' gradient accumulators (+= this call's dgamma /
  * dbeta), so the caller needs no separate accumulate pass per BatchNorm layer. */
 int sfod_bn_relu_pool_bwd(const void* dz, const void* y, const float* mean, const float* invstd,
@@ -299,6 +314,11 @@ int sfod_bn_relu_pool_bwd(const void* dz, const void* y, const float* mean, cons
 int sfod_bn_bwd_ws_floats(int M, int C);
 /* ---- ResNet-101-C4 backbone helpers (d2 build_resnet_backbone selected by the r101 yaml's missing
  * BACKBONE.NAME, configs/r101_c4_cs_foggy_adaptive_teacher_source_free.yaml:1-28) ----
+ * The pointwise kernels below (add_act, subsample2, maxpool3s2, act_bwd, add_inplace, add_act_bwd, mul_mask) are each ONE
+ * fp32 operation per element, rounded once (nearest even) to bf16 for bf16 data: bit for bit equal to the same torch
+ * operation in fp32 (tests/test_gpu_pointwise_definition.py), +-0, denormals and +-inf included.  NaN: sums and products
+ * propagate it; the ReLU of sfod_add_act (act 1) is fmaxf(v, 0) = +0 for a NaN and for -0, like the BatchNorm + ReLU
+ * kernels (pinned -- torch.relu would propagate the NaN); a gate (y > 0) is closed for y = NaN and y = -0.
  * out = act(a + b), act 0/1: residual join of BottleneckBlock (relu(conv3(x) + shortcut(x))); out_pairs (may be NULL,
  * fp32 data, n % 8 == 0 with 8-channel groups): the same values as operand pairs of type pairs_dt; out_pairs2 (may be NULL;
  * pairs_dt SFOD_F16X3): once more as SFOD_BF16X3 pairs */
@@ -321,9 +341,10 @@ int sfod_stem7x7(const float* x, const void* w_packed, const uint32_t* w_absmax,
  * SFOD_BF16X3 from fp32 input (the stem GEMM's operand pairs, written directly) */
 int sfod_im2col_stem(const void* x, void* out, int B, int H, int W, int Cp, int Kpad, int dt, int out_dt,
                      void* stream);
-/* BasicStem max_pool2d(kernel 3, stride 2, padding 1), forward (the stem is frozen) */
+/* BasicStem max_pool2d(kernel 3, stride 2, padding 1), forward (the stem is frozen).  The maximum of the window's in-map
+ * pixels by fmaxf from -inf: -inf is an ordinary value, a NaN is dropped (torch propagates it). */
 int sfod_maxpool3s2(const void* x, void* y, int B, int H, int W, int C, int dt, void* stream);
-/* elementwise: dx = dy * (y > 0) (ReLU) or dy * (y > 0 ? 1 : 0.2) (LeakyReLU) in place on dy */
+/* elementwise: dx = y > 0 ? dy : +0 (act 1, ReLU) or y > 0 ? dy : 0.2f * dy (act 2, LeakyReLU, the fp32 slope) in place on dy */
 int sfod_act_bwd(void* dy, const void* y, int64_t n, int act, int dt, void* stream);
 /* a += b  (fp32 or bf16 elementwise) */
 int sfod_add_inplace(void* a, const void* b, int64_t n, int dt, void* stream);
@@ -415,11 +436,18 @@ int sfod_make_rois(const float* props, const int32_t* prop_count, int B, int P, 
                    void* stream);
 
 /* ---- K13: ROIAlign (tv roi_align aligned=True, adaptive sampling; Appendix A.11) on NHWC
- * features.  out: [R, PH*PW, C] (dt).  rois with batch index < 0 produce zeros.  pooled in [1, 16] (the backward: [1, 8]). */
+ * features.  out: [R, PH*PW, C] (dt).  rois with batch index < 0 are padding rows: the forward writes zeros for them, the
+ * backward ignores them.  pooled in [1, 16] (the backward: [1, 8]).
+ * Definition (oracle/pointwise_definitions.py roi_align_matrices; held per element by tests/test_gpu_roi_definition.py, in
+ * fp32, bf16 and on the exact values of operand pairs): out[r, ph, pw, c] = sum_{py, px} Ay[r, ph, py] Ax[r, pw, px]
+ * feat[b_r, py, px, c] / count_r, Ay / Ax the bilinear weights of the bin's grid_h / grid_w sample rows / columns
+ * (grid = ceil(roi_len / pooled), count = max(grid_h grid_w, 1); a zero-sized ROI has grid 0 and gives zeros), sample
+ * coordinates in fp32 as torchvision writes them, a sample outside [-1, H] x [-1, W] dropped. */
 int sfod_roi_align_fwd(const void* feat, int B, int H, int W, int C, const float* rois, int R,
                        int pooled, float scale, void* out, int dt, void* stream);
-/* dfeat fp32 [B,H,W,C] += adjoint of the forward (zero-init by the caller); one workgroup per ROI,
- * separable interpolation weights, one float atomic per footprint pixel and channel */
+/* dfeat fp32 [B,H,W,C] += adjoint of the forward above (zero-init by the caller, or an earlier gradient to add to).
+ * pooled == 7: tiled gather, one owner per gradient element, ROIs summed in ROI order (bit-reproducible); other sizes: one
+ * workgroup per ROI, separable interpolation weights, one float atomic per footprint pixel and channel */
 int sfod_roi_align_bwd(const void* dout, int B, int H, int W, int C, const float* rois, int R,
                        int pooled, float scale, float* dfeat, int dt, void* stream);
 

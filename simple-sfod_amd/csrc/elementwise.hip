@@ -618,7 +618,7 @@ k_bn_relu_pool_fwd(const T* __restrict__ y, const float* __restrict__ mean, cons
     }
     float r[V];
 #pragma unroll
-    for (int i = 0; i < V; ++i) r[i] = RELU ? 0.f : -3.0e38f;  // relu floor doubles as the max identity
+    for (int i = 0; i < V; ++i) r[i] = RELU ? 0.f : -INFINITY;  // relu floor doubles as the max identity
     const int win = POOL ? 2 : 1;
 #pragma unroll
     for (int dy = 0; dy < win; ++dy)
@@ -1132,10 +1132,11 @@ extern "C" int sfod_bn_relu_pool_bwd(const void* dz, const void* y, const float*
   const int V = (dt == SFOD_F32) ? 4 : 8;            // reduce pass (reads only)
   const int VO = (dy_dt == SFOD_F32) ? 4 : 8;        // apply pass
   SFOD_REQUIRE(C >= 8 && C % VO == 0 && C / V <= 256, "bn_bwd: unsupported channel count");
-  SFOD_REQUIRE(dz && y && mean && invstd && gamma && beta && ws, "bn_bwd: null argument");
   const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
   const int cv = C / V, UL = 256 / cv;
   const int64_t units = (int64_t)B * Ho * Wo;
+  // a pooled map with no 2x2 window (H or W = 1) has an empty dz: every pixel is a leftover one, dgamma = dbeta = 0
+  SFOD_REQUIRE((dz || units == 0) && y && mean && invstd && gamma && beta && ws, "bn_bwd: null argument");
   int grid1 = (int)((units + UL - 1) / UL);
   if (grid1 > BNB_GRID_MAX) grid1 = BNB_GRID_MAX;
   if (grid1 < 1) grid1 = 1;
@@ -1311,6 +1312,8 @@ extern "C" int sfod_mul_mask(void* a, const uint8_t* mask, int64_t n, float scal
 // ResNet-C4 helpers (d2 build_resnet_backbone: BasicStem + BottleneckBlock)
 // ---------------------------------------------------------------------------------------------
 // out = act(a + b): the residual join of a bottleneck block (relu(conv3_bn(x) + shortcut))
+// act 1 is fmaxf(v, 0): +0 for a NaN and for -0, as in every BatchNorm + ReLU kernel of this file (pinned by
+// tests/test_gpu_pointwise_definition.py; torch.relu would propagate the NaN).  The backward gates (y > 0) agree: closed there.
 template <typename T>
 __global__ void k_add_act(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ o, int64_t nvec, int act) {
   constexpr int V = VecT<T>::N;
@@ -1495,7 +1498,7 @@ __global__ void k_maxpool3s2(const T* __restrict__ x, T* __restrict__ y, int B, 
     const int b = (int)(pix / Ho);
     float r[V];
 #pragma unroll
-    for (int i = 0; i < V; ++i) r[i] = -3.0e38f;
+    for (int i = 0; i < V; ++i) r[i] = -INFINITY;     // the max identity: -inf is an ordinary value (fmaxf drops a NaN)
     for (int dy = -1; dy <= 1; ++dy)
       for (int dx = -1; dx <= 1; ++dx) {
         const int iy = 2 * oy + dy, ix = 2 * ox + dx;
