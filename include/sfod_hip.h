@@ -542,6 +542,43 @@ int sfod_aug_erase(uint8_t* img, int C, int H, int W, int i, int j, int h, int w
 int sfod_sgd_ema(float* param, const float* grad, float* mom, float* teacher, int64_t n,
                  const float* lr, float momentum, float weight_decay, float grad_scale,
                  float ema_keep, float ema_one_minus_keep, int first_step, void* stream);
+/* ---- Solver options on the flat buffers (Detectron2 SOLVER.CLIP_GRADIENTS / NESTEROV / BIAS_LR_FACTOR /
+ * WEIGHT_DECAY_BIAS): a SEGMENT TABLE describes the parameter tensors inside the flat arrays.  All tables are DEVICE
+ * arrays of nseg entries:
+ *   seg_off  int64  first element of the segment; ascending, a multiple of 4 (16-byte lanes never straddle two segments)
+ *   seg_len  int64  number of elements, any value >= 0; seg_off[s] + seg_len[s] <= seg_off[s + 1] and <= n.  The lanes
+ *                   between the end of a segment and the next offset are padding.
+ *   seg_hp   fp32   [nseg][2] = {weight_decay, lr_factor}
+ *   coef     fp32   [nseg] clip coefficient, written by sfod_grad_clip_coef, read by sfod_sgd_ema_seg
+ * n (a multiple of 4) is the length of the flat arrays, which are 16-byte aligned.  The kernels bound every access by n,
+ * so a table that breaks the rules above gives wrong numbers, never an access outside the arrays.
+ *
+ * sfod_grad_clip_coef: coef[s] = what torch.nn.utils.clip_grad_norm_(p, clip_value, norm_type) computes for tensor s alone,
+ * of the gradient the optimiser applies (grad * grad_scale):  c = clip_value / (norm + 1e-6);  coef = c > 1 ? 1 : c.
+ * norm_type 0: 2-norm (sum of squares, sqrt); 1: max-norm.  Padding lanes are not read into the norm.  Two launches
+ * whatever nseg is: partials per 4096-element chunk of the flat array (one writer per slot, no atomics), then one
+ * workgroup per segment adds its partials in a fixed order -- the result is bit-identical from run to run.  No host read.
+ * Non-finite gradients: an infinity gives norm = inf and coef = 0; a NaN gives coef = NaN (the comparison keeps it,
+ * like torch).  ws: sfod_grad_clip_ws_floats(n, nseg) floats of device memory, need not be initialised.
+ *
+ * sfod_sgd_ema_seg: sfod_sgd_ema over [0, n) in ONE launch with per-segment hyper-parameters.  Per element
+ *   g' = grad * grad_scale
+ *   clip_type 1 ("value"): g' = clamp(g', -clip_value, clip_value), NaN stays NaN
+ *   clip_type 2 ("norm"):  g' = grad * (grad_scale * coef[s])   (the coefficient folded into the scale: with coef == 1
+ *                          the update is bit-identical to clip_type 0; an infinite gradient under coef == 0 becomes NaN)
+ *   gr = g' + weight_decay[s] * p;   m = first_step ? gr : momentum * m + gr;   d = nesterov ? gr + momentum * m : m
+ *   p -= (lr * lr_factor[s]) * d;    teacher = p * (1 - k) + teacher * k  as in sfod_sgd_ema (teacher may be NULL).
+ * An element belongs to the last segment whose offset is <= its index, so padding lanes are updated with their
+ * segment's values like sfod_sgd_ema does (they hold zeros and keep them).  clip_coef may be NULL unless clip_type == 2.
+ * With clip_type 0, nesterov 0 and every lr_factor 1 the result equals sfod_sgd_ema's bit for bit. */
+int64_t sfod_grad_clip_ws_floats(int64_t n, int nseg);
+int sfod_grad_clip_coef(const float* grad, int64_t n, const int64_t* seg_off, const int64_t* seg_len, int nseg,
+                        float grad_scale, float clip_value, int norm_type, float* coef, float* ws,
+                        int64_t ws_floats, void* stream);
+int sfod_sgd_ema_seg(float* param, const float* grad, float* mom, float* teacher, int64_t n,
+                     const int64_t* seg_off, int nseg, const float* seg_hp, const float* clip_coef,
+                     const float* lr, float momentum, float grad_scale, int clip_type, float clip_value,
+                     int nesterov, float ema_keep, float ema_one_minus_keep, int first_step, void* stream);
 /* t = s*(1-k) + t*k  on fp32 buffers (BN running stats) */
 int sfod_ema(float* teacher, const float* student, int64_t n, float keep, float one_minus_keep, void* stream);
 /* the same update on the int64 buffers (num_batches_tracked): fp32 arithmetic, truncated on the way back like the

@@ -2079,6 +2079,230 @@ extern "C" int sfod_sgd_ema(float* param, const float* grad, float* mom, float* 
   return sfod_check_launch("sgd_ema");
 }
 
+// ---------------------------------------------------------------------------------------------
+// Solver options over the flat buffers: per-segment gradient clipping coefficients (two launches) and the
+// table-driven form of k_sgd_ema (per-segment weight decay / lr factor / clip coefficient, Nesterov), one launch.
+// A segment = one parameter tensor: seg_off[s] (a multiple of 4, ascending), seg_len[s] elements.  Both passes cut the
+// flat buffer into chunks of SOLVER_CHUNK floats, one workgroup each; a workgroup finds the segments of its chunk by
+// bisection of seg_off (block-uniform: scalar loads), so the work follows the position in the buffer and not the
+// segment sizes (64 ... 25.7 M elements).
+// ---------------------------------------------------------------------------------------------
+#define SOLVER_CHUNK 4096
+
+// the last segment of [lo, hi] whose offset is <= x (lo when none)
+__device__ __forceinline__ int seg_of(const int64_t* __restrict__ seg_off, int lo, int hi, int64_t x) {
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (seg_off[mid] <= x) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+// max that keeps a NaN from either side (fmaxf drops it; torch's max-norm does not)
+__device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
+// sum (INF = false) or NaN-keeping max (INF = true) over the 256 threads, in a fixed order; the result is valid in thread 0
+template <bool INF>
+__device__ __forceinline__ float solver_block_reduce(float v, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float u = __shfl_xor(v, o);
+    v = INF ? nan_max(v, u) : v + u;
+  }
+  __syncthreads();                                   // red[] of the previous segment has been read
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (INF) return nan_max(nan_max(red[0], red[1]), nan_max(red[2], red[3]));
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// stage 1: partial[c + s] = sum of (g * gscale)^2 (or max |g * gscale|) over chunk c's part of segment s.  The slot
+// index c + s is unique per (chunk, segment) pair because both only grow along the buffer; slots no pair maps to are
+// never read.  No atomics: every slot has one writer.
+template <bool INF>
+__global__ void __launch_bounds__(256)
+k_grad_seg_partials(const float* __restrict__ g, int64_t n, const int64_t* __restrict__ seg_off,
+                    const int64_t* __restrict__ seg_len, int nseg, float gscale, float* __restrict__ partial) {
+  __shared__ float red[4];
+  const int64_t c = blockIdx.x;
+  const int64_t c0 = c * SOLVER_CHUNK;
+  const int64_t c1 = c0 + SOLVER_CHUNK < n ? c0 + SOLVER_CHUNK : n;
+  const int s0 = seg_of(seg_off, 0, nseg - 1, c0);
+  const int s1 = seg_of(seg_off, s0, nseg - 1, c1 - 1);
+  for (int s = s0; s <= s1; ++s) {
+    int64_t a = seg_off[s], b = a + seg_len[s];
+    if (a < c0) a = c0;
+    if (b > c1) b = c1;
+    float acc = 0.f;
+    // whole float4s (n % 4 == 0, g 16-byte aligned); lanes outside [a, b) are masked, so the padding need not be zero
+    for (int64_t v = (a >> 2) + threadIdx.x; v * 4 < b; v += 256) {
+      const float4 gv = reinterpret_cast<const float4*>(g)[v];
+      const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int64_t i = v * 4 + k;
+        if (i >= a && i < b) {
+          const float x = gg[k] * gscale;
+          acc = INF ? nan_max(acc, fabsf(x)) : acc + x * x;
+        }
+      }
+    }
+    acc = solver_block_reduce<INF>(acc, red);
+    if (threadIdx.x == 0) partial[c + s] = acc;
+  }
+}
+
+// stage 2: one workgroup per segment adds (or maxes) the segment's partials in a fixed order and writes
+// coef[s] = min(1, clip / (norm + 1e-6)) the way torch.nn.utils.clip_grad_norm_ forms it; NaN stays NaN
+template <bool INF>
+__global__ void __launch_bounds__(256)
+k_grad_seg_coef(const float* __restrict__ partial, int64_t n, const int64_t* __restrict__ seg_off,
+                const int64_t* __restrict__ seg_len, float clip, float* __restrict__ coef) {
+  __shared__ float red[4];
+  const int s = blockIdx.x;
+  int64_t a = seg_off[s], b = a + seg_len[s];
+  if (a < 0) a = 0;
+  if (b > n) b = n;
+  float acc = 0.f;
+  if (b > a) {
+    const int64_t cl = (b - 1) / SOLVER_CHUNK;
+    for (int64_t c = a / SOLVER_CHUNK + threadIdx.x; c <= cl; c += 256) {
+      const float v = partial[c + s];
+      acc = INF ? nan_max(acc, v) : acc + v;
+    }
+  }
+  acc = solver_block_reduce<INF>(acc, red);
+  if (threadIdx.x == 0) {
+    const float norm = INF ? acc : __fsqrt_rn(acc);
+    const float cf = __fdiv_rn(clip, norm + 1e-6f);
+    coef[s] = cf > 1.f ? 1.f : cf;                   // not fminf: a NaN norm gives a NaN coefficient
+  }
+}
+
+extern "C" int64_t sfod_grad_clip_ws_floats(int64_t n, int nseg) {
+  SFOD_REQUIRE(sfod_i64s_ok({n}) && sfod_ints_ok({nseg}), "grad_clip_ws_floats: negative or oversized extent");
+  return (n + SOLVER_CHUNK - 1) / SOLVER_CHUNK + nseg;
+}
+
+extern "C" int sfod_grad_clip_coef(const float* grad, int64_t n, const int64_t* seg_off, const int64_t* seg_len,
+                                   int nseg, float grad_scale, float clip_value, int norm_type, float* coef,
+                                   float* ws, int64_t ws_floats, void* stream) {
+  SFOD_REQUIRE(sfod_i64s_ok({n, ws_floats}) && sfod_ints_ok({nseg}), "grad_clip_coef: negative or oversized extent");
+  SFOD_REQUIRE(n % 4 == 0, "grad_clip_coef: n must be a multiple of 4 (the flat buffer pads every segment to a float4)");
+  SFOD_REQUIRE(norm_type == 0 || norm_type == 1, "grad_clip_coef: norm_type must be 0 (2-norm) or 1 (max-norm)");
+  if (nseg == 0) return 0;
+  SFOD_REQUIRE(seg_off != nullptr && seg_len != nullptr && coef != nullptr, "grad_clip_coef: null argument (seg_off, seg_len, coef)");
+  SFOD_REQUIRE(n == 0 || (grad != nullptr && ws != nullptr), "grad_clip_coef: null argument (grad, ws)");
+  SFOD_REQUIRE(((uintptr_t)grad & 15) == 0, "grad_clip_coef: grad must be 16-byte aligned");
+  const int64_t chunks = (n + SOLVER_CHUNK - 1) / SOLVER_CHUNK;
+  SFOD_REQUIRE(ws_floats >= chunks + nseg, "grad_clip_coef: workspace smaller than sfod_grad_clip_ws_floats(n, nseg)");
+  hipStream_t s = (hipStream_t)stream;
+  if (chunks > 0) {
+    if (norm_type == 1)
+      hipLaunchKernelGGL(k_grad_seg_partials<true>, dim3((unsigned)chunks), dim3(256), 0, s, grad, n, seg_off, seg_len,
+                         nseg, grad_scale, ws);
+    else
+      hipLaunchKernelGGL(k_grad_seg_partials<false>, dim3((unsigned)chunks), dim3(256), 0, s, grad, n, seg_off, seg_len,
+                         nseg, grad_scale, ws);
+  }
+  if (norm_type == 1)
+    hipLaunchKernelGGL(k_grad_seg_coef<true>, dim3(nseg), dim3(256), 0, s, ws, n, seg_off, seg_len, clip_value, coef);
+  else
+    hipLaunchKernelGGL(k_grad_seg_coef<false>, dim3(nseg), dim3(256), 0, s, ws, n, seg_off, seg_len, clip_value, coef);
+  return sfod_check_launch("grad_clip_coef");
+}
+
+// k_sgd_ema with the hyper-parameters read per segment: seg_hp[2s] weight decay, seg_hp[2s + 1] lr factor, coef[s] the
+// clip coefficient (CLIP == 2).  CLIP == 0 / 2 keep k_sgd_ema's expression (the coefficient is folded into the gradient
+// scale: exactly grad_scale when it is 1), so a table that spells out the two weight-decay groups reproduces it bit for bit.
+template <int CLIP, bool NESTEROV>
+__global__ void __launch_bounds__(256)
+k_sgd_ema_seg(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ t,
+              int64_t n, const int64_t* __restrict__ seg_off, int nseg, const float* __restrict__ seg_hp,
+              const float* __restrict__ coef, const float* __restrict__ lr_ptr, float momentum, float gscale,
+              float clip, float keep, float one_minus_keep, int first) {
+  const float lr = lr_ptr[0];
+  const int64_t c0 = (int64_t)blockIdx.x * SOLVER_CHUNK;
+  const int64_t c1 = c0 + SOLVER_CHUNK < n ? c0 + SOLVER_CHUNK : n;
+  const int s0 = seg_of(seg_off, 0, nseg - 1, c0);
+  const int s1 = seg_of(seg_off, s0, nseg - 1, c1 - 1);
+  for (int64_t i = (c0 >> 2) + threadIdx.x; i * 4 < c1; i += 256) {
+    const int s = seg_of(seg_off, s0, s1, i * 4);      // a float4 never straddles two segments
+    const float wd = seg_hp[2 * s], lrs = lr * seg_hp[2 * s + 1];
+    const float sc = CLIP == 2 ? gscale * coef[s] : gscale;
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = first ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<float4*>(m)[i];
+    float pp[4] = {pv.x, pv.y, pv.z, pv.w};
+    const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+    float mm[4] = {mv.x, mv.y, mv.z, mv.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float gr;
+      if (CLIP == 1) {
+        float x = gg[k] * gscale;
+        x = x > clip ? clip : x;                       // comparisons, not fminf / fmaxf: NaN stays NaN
+        x = x < -clip ? -clip : x;
+        gr = x + wd * pp[k];
+      } else {
+        gr = gg[k] * sc + wd * pp[k];
+      }
+      mm[k] = first ? gr : mm[k] * momentum + gr;
+      const float d = NESTEROV ? gr + momentum * mm[k] : mm[k];
+      pp[k] = pp[k] - lrs * d;
+    }
+    reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
+    reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+    if (t) {
+      float4 tv = reinterpret_cast<float4*>(t)[i];
+      tv.x = ema_mix(pp[0], one_minus_keep, tv.x, keep);
+      tv.y = ema_mix(pp[1], one_minus_keep, tv.y, keep);
+      tv.z = ema_mix(pp[2], one_minus_keep, tv.z, keep);
+      tv.w = ema_mix(pp[3], one_minus_keep, tv.w, keep);
+      reinterpret_cast<float4*>(t)[i] = tv;
+    }
+  }
+}
+
+template <int CLIP, bool NESTEROV>
+static void launch_sgd_ema_seg(hipStream_t s, float* p, const float* g, float* m, float* t, int64_t n,
+                               const int64_t* seg_off, int nseg, const float* seg_hp, const float* coef, const float* lr,
+                               float momentum, float gscale, float clip, float keep, float omk, int first) {
+  hipLaunchKernelGGL((k_sgd_ema_seg<CLIP, NESTEROV>), dim3((unsigned)((n + SOLVER_CHUNK - 1) / SOLVER_CHUNK)), dim3(256), 0,
+                     s, p, g, m, t, n, seg_off, nseg, seg_hp, coef, lr, momentum, gscale, clip, keep, omk, first);
+}
+
+extern "C" int sfod_sgd_ema_seg(float* param, const float* grad, float* mom, float* teacher, int64_t n,
+                                const int64_t* seg_off, int nseg, const float* seg_hp, const float* clip_coef,
+                                const float* lr, float momentum, float grad_scale, int clip_type, float clip_value,
+                                int nesterov, float ema_keep, float ema_one_minus_keep, int first_step, void* stream) {
+  SFOD_REQUIRE(sfod_i64s_ok({n}) && sfod_ints_ok({nseg}), "sgd_ema_seg: negative or oversized extent");
+  SFOD_REQUIRE(n % 4 == 0, "sgd_ema_seg: n must be a multiple of 4 (the flat buffer pads every segment to a float4)");
+  SFOD_REQUIRE(clip_type >= 0 && clip_type <= 2, "sgd_ema_seg: clip_type must be 0 (none), 1 (value) or 2 (norm)");
+  SFOD_REQUIRE(param != nullptr && grad != nullptr && mom != nullptr && lr != nullptr, "sgd_ema_seg: null argument (param, grad, mom, lr)");
+  SFOD_REQUIRE(nseg >= 1 && seg_off != nullptr && seg_hp != nullptr, "sgd_ema_seg: no segment table (nseg, seg_off, seg_hp)");
+  SFOD_REQUIRE(clip_type != 2 || clip_coef != nullptr, "sgd_ema_seg: clip_type 2 needs clip_coef");
+  SFOD_REQUIRE(clip_type != 1 || clip_value >= 0.f, "sgd_ema_seg: clip_type 1 needs clip_value >= 0");
+  SFOD_REQUIRE((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)mom | (uintptr_t)teacher) & 15) == 0,
+               "sgd_ema_seg: param, grad, mom and teacher must be 16-byte aligned");
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+#define SFOD_SEG_LAUNCH(C, N)                                                                                       \
+  launch_sgd_ema_seg<C, N>(s, param, grad, mom, teacher, n, seg_off, nseg, seg_hp, clip_coef, lr, momentum, grad_scale, \
+                           clip_value, ema_keep, ema_one_minus_keep, first_step)
+  if (nesterov) {
+    if (clip_type == 0) SFOD_SEG_LAUNCH(0, true);
+    else if (clip_type == 1) SFOD_SEG_LAUNCH(1, true);
+    else SFOD_SEG_LAUNCH(2, true);
+  } else {
+    if (clip_type == 0) SFOD_SEG_LAUNCH(0, false);
+    else if (clip_type == 1) SFOD_SEG_LAUNCH(1, false);
+    else SFOD_SEG_LAUNCH(2, false);
+  }
+#undef SFOD_SEG_LAUNCH
+  return sfod_check_launch("sgd_ema_seg");
+}
+
 __global__ void k_ema(float* __restrict__ t, const float* __restrict__ s, int64_t n, float keep, float omk) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     t[i] = ema_mix(s[i], omk, t[i], keep);

@@ -10,8 +10,16 @@ applies  g += wd*p ; m = mu*m + g ; p -= lr*m  and -- when a teacher is attached
 t = (1-k)*p + k*t  in the same pass (each value read once).  The flat gradient buffer is also the
 single RCCL all-reduce payload of the data-parallel step.  The learning rate lives in a device
 scalar, so the schedule never synchronises the stream.
+
+Detectron2's further solver options (CLIP_GRADIENTS per tensor by value or norm, NESTEROV, BIAS_LR_FACTOR,
+WEIGHT_DECAY_BIAS) switch ``FusedSGD.step`` to ONE table-driven launch over the optimised range: a device table
+built once holds {offset, length, weight decay, lr factor} per parameter tensor, and norm clipping adds a
+two-launch segmented reduction over the flat gradient that fills the per-tensor clip coefficients.  With none of
+them set the two-group path above runs unchanged.  ``WarmupCosineLR`` and WARMUP_METHOD "constant" complete the
+schedulers (``build_lr_scheduler``).
 """
 import bisect
+import math
 from collections import OrderedDict
 
 import torch
@@ -105,12 +113,68 @@ class FlatModelState:
             p.grad = self.grad[o:o + k].view(shp)
 
 
-class FusedSGD:
-    """torch.optim-like facade (zero_grad / step / param_groups / state_dict) over FlatModelState."""
+def segment_hyper_params(flat, weight_decay, weight_decay_norm, bias_lr_factor=1.0, weight_decay_bias=None):
+    """Detectron2's ``get_default_optimizer_params`` for the optimised parameters of ``flat``, in flat-buffer order:
+    -> [(name, offset, numel, weight_decay, lr_factor)].  Start from WEIGHT_DECAY; a norm module's own parameters take
+    WEIGHT_DECAY_NORM; then a parameter whose own name is ``bias`` takes WEIGHT_DECAY_BIAS when that is not None (this
+    overrides the norm value) and lr_factor = BIAS_LR_FACTOR."""
+    rows = []
+    for n, (o, k, _) in flat.offsets.items():
+        if o >= flat.n_norm_end:          # frozen: not optimised
+            continue
+        wd, lf = (weight_decay_norm if o >= flat.n_decay else weight_decay), 1.0
+        if n.rsplit(".", 1)[-1] == "bias":
+            if weight_decay_bias is not None:
+                wd = weight_decay_bias
+            lf = bias_lr_factor
+        rows.append((n, o, k, float(wd), float(lf)))
+    return rows
 
-    def __init__(self, flat, lr, momentum=0.9, weight_decay=1e-4, weight_decay_norm=0.0):
+
+def clip_options(cfg):
+    """SOLVER.CLIP_GRADIENTS -> None (off) or {"type": "value" | "norm", "value": CLIP_VALUE, "norm_type": 2.0 | inf};
+    anything else is a ValueError naming the key."""
+    c = cfg.SOLVER.CLIP_GRADIENTS
+    if not c.ENABLED:
+        return None
+    if c.CLIP_TYPE not in ("value", "norm"):
+        raise ValueError("SOLVER.CLIP_GRADIENTS.CLIP_TYPE = {!r} is not supported (\"value\" or \"norm\")".format(c.CLIP_TYPE))
+    if not float(c.CLIP_VALUE) >= 0.0:
+        raise ValueError("SOLVER.CLIP_GRADIENTS.CLIP_VALUE = {!r} is not supported (>= 0)".format(c.CLIP_VALUE))
+    norm_type = float(c.NORM_TYPE)
+    if c.CLIP_TYPE == "norm" and norm_type not in native.NORM_TYPES:
+        raise ValueError("SOLVER.CLIP_GRADIENTS.NORM_TYPE = {!r} is not supported (2.0 or inf)".format(c.NORM_TYPE))
+    return {"type": c.CLIP_TYPE, "value": float(c.CLIP_VALUE), "norm_type": norm_type}
+
+
+class FusedSGD:
+    """torch.optim-like facade (zero_grad / step / param_groups / state_dict) over FlatModelState.
+
+    ``nesterov``, ``clip`` (see ``clip_options``), ``bias_lr_factor`` and ``weight_decay_bias`` are Detectron2's solver
+    options.  With none of them set, ``step`` is the two ``sgd_ema_`` launches (one per weight-decay group).  Otherwise
+    it is ONE ``sgd_ema_seg_`` launch over the optimised range, driven by a per-parameter device table built here once
+    ({weight decay, lr factor} per tensor), preceded for ``clip["type"] == "norm"`` by the two launches of
+    ``grad_clip_coef_``; no torch kernels, no host read."""
+
+    def __init__(self, flat, lr, momentum=0.9, weight_decay=1e-4, weight_decay_norm=0.0, nesterov=False, clip=None,
+                 bias_lr_factor=1.0, weight_decay_bias=None):
         self.flat = flat
         self.momentum, self.weight_decay, self.weight_decay_norm = momentum, weight_decay, weight_decay_norm
+        self.nesterov, self.clip = bool(nesterov), clip
+        if self.nesterov and not momentum > 0:
+            raise ValueError("SOLVER.NESTEROV needs SOLVER.MOMENTUM > 0, got {!r}".format(momentum))
+        self.hyper = segment_hyper_params(flat, weight_decay, weight_decay_norm, bias_lr_factor, weight_decay_bias)
+        plain = segment_hyper_params(flat, weight_decay, weight_decay_norm)
+        self.table_driven = bool(self.hyper) and (self.nesterov or clip is not None or self.hyper != plain)
+        if self.table_driven:
+            dev = flat.param.device
+            self.seg_off = torch.tensor([r[1] for r in self.hyper], dtype=torch.int64, device=dev)
+            self.seg_len = torch.tensor([r[2] for r in self.hyper], dtype=torch.int64, device=dev)
+            self.seg_hp = torch.tensor([[r[3], r[4]] for r in self.hyper], dtype=torch.float32, device=dev)
+            self.clip_coef = self.clip_ws = None
+            if clip is not None and clip["type"] == "norm":
+                self.clip_coef = torch.ones(len(self.hyper), dtype=torch.float32, device=dev)
+                self.clip_ws = native.grad_clip_ws(flat.n_norm_end, len(self.hyper), dev)
         self.mom = torch.zeros_like(flat.param)
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=flat.param.device)
         self.param_groups = [{"lr": float(lr), "initial_lr": float(lr)}]
@@ -151,11 +215,21 @@ class FusedSGD:
                 p.grad = f.grad[o:o + k].view(shp)
         first = self._steps == 0
         t = self.teacher.param if (self.teacher is not None and ema) else None
-        segs = [(0, f.n_decay, self.weight_decay), (f.n_decay, f.n_norm_end, self.weight_decay_norm)]
-        for a, b, wd in segs:
-            if b > a:
-                native.sgd_ema_(f.param[a:b], f.grad[a:b], self.mom[a:b], None if t is None else t[a:b],
-                                self.lr_dev, self.momentum, wd, self.grad_scale, self.ema_keep, first)
+        if self.table_driven:
+            b, clip = f.n_norm_end, self.clip
+            if self.clip_coef is not None:
+                native.grad_clip_coef_(self.clip_coef, f.grad[:b], self.seg_off, self.seg_len, self.grad_scale,
+                                       clip["value"], clip["norm_type"], self.clip_ws)
+            native.sgd_ema_seg_(f.param[:b], f.grad[:b], self.mom[:b], None if t is None else t[:b], self.seg_off,
+                                self.seg_hp, self.clip_coef, self.lr_dev, self.momentum, self.grad_scale,
+                                clip["type"] if clip else None, clip["value"] if clip else 0.0, self.nesterov,
+                                self.ema_keep, first)
+        else:
+            segs = [(0, f.n_decay, self.weight_decay), (f.n_decay, f.n_norm_end, self.weight_decay_norm)]
+            for a, b, wd in segs:
+                if b > a:
+                    native.sgd_ema_(f.param[a:b], f.grad[a:b], self.mom[a:b], None if t is None else t[a:b],
+                                    self.lr_dev, self.momentum, wd, self.grad_scale, self.ema_keep, first)
         if t is not None:
             if f.n_total > f.n_norm_end:  # frozen (never updated) parameters still take part in the EMA
                 native.ema_(t[f.n_norm_end:f.n_total], f.param[f.n_norm_end:f.n_total], self.ema_keep)
@@ -259,40 +333,46 @@ class FusedSGD:
 
 
 def build_optimizer(cfg, model, frozen=None):
-    """d2 build_optimizer for SOLVER.{BASE_LR,MOMENTUM,WEIGHT_DECAY,WEIGHT_DECAY_NORM}.  ``frozen``: parameter prefixes that
-    never receive a gradient in this trainer (default: the discriminators when DOMAIN_CLASSIFIER is off)."""
+    """d2 build_optimizer for SOLVER.{BASE_LR,MOMENTUM,NESTEROV,WEIGHT_DECAY,WEIGHT_DECAY_NORM,WEIGHT_DECAY_BIAS,
+    BIAS_LR_FACTOR,CLIP_GRADIENTS} (per-tensor clipping, as d2's wrapped ``optimizer.step``).  ``frozen``: parameter prefixes
+    that never receive a gradient in this trainer (default: the discriminators when DOMAIN_CLASSIFIER is off)."""
     if frozen is None:
         frozen = ()
         if "DOMAIN_CLASSIFIER" in cfg and not cfg.DOMAIN_CLASSIFIER.ENABLED:
             # the domain branch never runs: the reference leaves these grads None and SGD skips them
             frozen = ("DC_img.", "DC_ins.")
+    clip = clip_options(cfg)              # validated before anything is allocated
     flat = FlatModelState(model, frozen_prefixes=frozen)
-    assert cfg.SOLVER.BIAS_LR_FACTOR == 1.0 and cfg.SOLVER.WEIGHT_DECAY_BIAS in (None, cfg.SOLVER.WEIGHT_DECAY)
-    assert not cfg.SOLVER.CLIP_GRADIENTS.ENABLED and not cfg.SOLVER.NESTEROV
     return FusedSGD(flat, cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM, cfg.SOLVER.WEIGHT_DECAY,
-                    cfg.SOLVER.WEIGHT_DECAY_NORM)
+                    cfg.SOLVER.WEIGHT_DECAY_NORM, nesterov=cfg.SOLVER.NESTEROV, clip=clip,
+                    bias_lr_factor=cfg.SOLVER.BIAS_LR_FACTOR, weight_decay_bias=cfg.SOLVER.WEIGHT_DECAY_BIAS)
 
 
-class WarmupMultiStepLR:
-    """d2 WarmupMultiStepLR; steps beyond MAX_ITER are dropped (the yamls list 360000 > 100000)."""
+class _WarmupLR:
+    """Shared part of the d2 schedulers: the warm-up factor (WARMUP_METHOD "linear" or "constant") times ``_decay(it)``."""
 
     def __init__(self, optimizer, cfg):
         self.optimizer = optimizer
         self.base_lr = cfg.SOLVER.BASE_LR
-        self.milestones = sorted(s for s in cfg.SOLVER.STEPS if s <= cfg.SOLVER.MAX_ITER)
-        self.gamma = cfg.SOLVER.GAMMA
         self.warmup_factor = cfg.SOLVER.WARMUP_FACTOR
         self.warmup_iters = cfg.SOLVER.WARMUP_ITERS
-        assert cfg.SOLVER.WARMUP_METHOD == "linear" and cfg.SOLVER.LR_SCHEDULER_NAME == "WarmupMultiStepLR"
+        self.warmup_method = cfg.SOLVER.WARMUP_METHOD
+        if self.warmup_method not in ("linear", "constant"):
+            raise ValueError("SOLVER.WARMUP_METHOD = {!r} is not supported (\"linear\" or \"constant\")".format(
+                self.warmup_method))
         self.last_epoch = 0
         self.optimizer.set_lr(self.get_lr(0))
 
+    def _warmup(self, it):
+        if it >= self.warmup_iters:
+            return 1.0
+        if self.warmup_method == "constant":
+            return self.warmup_factor
+        alpha = it / self.warmup_iters
+        return self.warmup_factor * (1 - alpha) + alpha
+
     def get_lr(self, it):
-        f = 1.0
-        if it < self.warmup_iters:
-            alpha = it / self.warmup_iters
-            f = self.warmup_factor * (1 - alpha) + alpha
-        return self.base_lr * f * self.gamma ** bisect.bisect_right(self.milestones, it)
+        return self.base_lr * self._warmup(it) * self._decay(it)
 
     def step(self):
         self.last_epoch += 1
@@ -304,3 +384,36 @@ class WarmupMultiStepLR:
     def load_state_dict(self, sd):
         self.last_epoch = sd["last_epoch"]
         self.optimizer.set_lr(self.get_lr(self.last_epoch))
+
+
+class WarmupMultiStepLR(_WarmupLR):
+    """d2 WarmupMultiStepLR; steps beyond MAX_ITER are dropped (the yamls list 360000 > 100000)."""
+
+    def __init__(self, optimizer, cfg):
+        self.milestones = sorted(s for s in cfg.SOLVER.STEPS if s <= cfg.SOLVER.MAX_ITER)
+        self.gamma = cfg.SOLVER.GAMMA
+        super().__init__(optimizer, cfg)
+
+    def _decay(self, it):
+        return self.gamma ** bisect.bisect_right(self.milestones, it)
+
+
+class WarmupCosineLR(_WarmupLR):
+    """d2 WarmupCosineLR: 0.5 * (1 + cos(pi * it / MAX_ITER)) times the warm-up factor."""
+
+    def __init__(self, optimizer, cfg):
+        self.max_iter = cfg.SOLVER.MAX_ITER
+        super().__init__(optimizer, cfg)
+
+    def _decay(self, it):
+        return 0.5 * (1.0 + math.cos(math.pi * it / self.max_iter))
+
+
+def build_lr_scheduler(cfg, optimizer):
+    """d2 build_lr_scheduler: SOLVER.LR_SCHEDULER_NAME -> scheduler."""
+    name = cfg.SOLVER.LR_SCHEDULER_NAME
+    if name == "WarmupMultiStepLR":
+        return WarmupMultiStepLR(optimizer, cfg)
+    if name == "WarmupCosineLR":
+        return WarmupCosineLR(optimizer, cfg)
+    raise ValueError("SOLVER.LR_SCHEDULER_NAME = {!r} is not supported (WarmupMultiStepLR or WarmupCosineLR)".format(name))

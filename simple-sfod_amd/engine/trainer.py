@@ -36,7 +36,7 @@ from ..modeling import build_model
 from ..modeling import offchain
 from ..modeling.batched import BatchedGT
 from ..structures import Boxes, Instances
-from .solver import FlatModelState, WarmupMultiStepLR, build_optimizer
+from .solver import FlatModelState, build_lr_scheduler, build_optimizer
 
 WRITER_PERIOD = 20  # hooks.PeriodicWriter(period=20), source_free_adaptive_teacher.py:679
 
@@ -388,7 +388,7 @@ class BaseTrainer:
             load_model_weights(self.model, cfg.MODEL.WEIGHTS, who="model")
         self._broadcast_initial_state()
         self._attach_reducer()
-        self.scheduler = WarmupMultiStepLR(self.optimizer, cfg)
+        self.scheduler = build_lr_scheduler(cfg, self.optimizer)
         self.data_loader = data_loader or self.build_train_loader(cfg)
         self._data_loader_iter = iter(self.data_loader)
         self.start_iter, self.max_iter = 0, cfg.SOLVER.MAX_ITER
@@ -764,7 +764,7 @@ class SourceFreeAdaptiveTeacherTrainer(BaseTrainer):
             self.optimizer.attach_teacher(self.teacher_flat, cfg.SFOD.EMA.KEEP_RATE)
         for p in self.model_teacher.parameters():
             p.requires_grad_(False)
-        self.scheduler = WarmupMultiStepLR(self.optimizer, cfg)
+        self.scheduler = build_lr_scheduler(cfg, self.optimizer)
         self.start_iter, self.max_iter = 0, cfg.SOLVER.MAX_ITER
         self.iter = 0
         self.storage = EventStorage(0)

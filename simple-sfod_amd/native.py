@@ -1257,6 +1257,33 @@ def sgd_ema_(param, grad, mom, teacher, lr, momentum, weight_decay, grad_scale, 
          float(grad_scale), float(ema_keep), float(1.0 - float(ema_keep)), int(first_step))
 
 
+CLIP_TYPES = {None: 0, "value": 1, "norm": 2}      # sfod_sgd_ema_seg's clip_type
+NORM_TYPES = {2.0: 0, float("inf"): 1}             # sfod_grad_clip_coef's norm_type
+
+
+def grad_clip_ws(n, nseg, device):
+    """Workspace of ``grad_clip_coef_`` for a flat gradient of ``n`` elements in ``nseg`` segments (allocate once)."""
+    return torch.empty(query("sfod_grad_clip_ws_floats", int(n), int(nseg)), dtype=torch.float32, device=device)
+
+
+def grad_clip_coef_(coef, grad, seg_off, seg_len, grad_scale, clip_value, norm_type, ws):
+    """coef[s] <- clip_grad_norm_'s coefficient of segment s of ``grad * grad_scale`` (include/sfod_hip.h; two launches)."""
+    assert seg_off.dtype == torch.int64 and seg_len.dtype == torch.int64 and coef.dtype == torch.float32
+    assert seg_len.numel() == seg_off.numel() == coef.numel()
+    call("sfod_grad_clip_coef", grad, grad.numel(), seg_off, seg_len, seg_off.numel(), float(grad_scale),
+         float(clip_value), NORM_TYPES[float(norm_type)], coef, ws, ws.numel())
+
+
+def sgd_ema_seg_(param, grad, mom, teacher, seg_off, seg_hp, clip_coef, lr, momentum, grad_scale, clip_type, clip_value,
+                 nesterov, ema_keep, first_step):
+    """``sgd_ema_`` in one launch with per-segment {weight decay, lr factor} (``seg_hp`` [nseg, 2]) and clipping:
+    ``clip_type`` None / "value" / "norm" (the latter reads ``clip_coef``, see ``grad_clip_coef_``)."""
+    assert seg_off.dtype == torch.int64 and seg_hp.dtype == torch.float32 and seg_hp.numel() == 2 * seg_off.numel()
+    call("sfod_sgd_ema_seg", param, grad, mom, teacher, param.numel(), seg_off, seg_off.numel(), seg_hp, clip_coef, lr,
+         float(momentum), float(grad_scale), CLIP_TYPES[clip_type], float(clip_value), int(bool(nesterov)),
+         float(ema_keep), float(1.0 - float(ema_keep)), int(first_step))
+
+
 def ema_(teacher, student, keep):
     call("sfod_ema", teacher, student, teacher.numel(), float(keep), float(1.0 - float(keep)))
 
