@@ -363,6 +363,11 @@ int sfod_mul_mask(void* a, const uint8_t* mask, int64_t n, float scale, int dt, 
 int sfod_rpn_decode(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
                     int Wf, int stride, const int32_t* image_sizes, float* props, float* scores,
                     int32_t* flags, void* stream);
+/* General form: Box2BoxTransform weights (wx, wy, ww, wh) = MODEL.RPN.BBOX_REG_WEIGHTS by value (finite, > 0, else
+ * SFOD_EBADARG).  sfod_rpn_decode is this call with (1, 1, 1, 1): one kernel, bit-identical results. */
+int sfod_rpn_decode_opt(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
+                        int Wf, int stride, const int32_t* image_sizes, float* props, float* scores,
+                        int32_t* flags, float wx, float wy, float ww, float wh, void* stream);
 /* stable descending segmented sort of B segments of n floats; out_idx int32 [B,n].
  * ws: workspace of sfod_sort_ws_bytes(B,n) bytes. */
 int64_t sfod_sort_ws_bytes(int B, int n);
@@ -420,6 +425,32 @@ int sfod_rpn_loss(const float* rpn_out, int ld, const float* cell_anchors, int A
                   int Wf, int stride, const int8_t* labels, const int32_t* matched,
                   const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
                   float* loss, const float* grad_scale, float* d_rpn_out, float* ws, void* stream);
+/* ---- Box-regression options (d2 _dense_box_regression_loss / FastRCNNOutputLayers.box_reg_loss, fvcore
+ * smooth_l1_loss / giou_loss).  The `_opt` entry points below take, by value:
+ *   wx, wy, ww, wh  Box2BoxTransform weights (BBOX_REG_WEIGHTS); finite and > 0.
+ *   loss_type       0 smooth-L1, 1 GIoU (BBOX_REG_LOSS_TYPE); anything else: SFOD_EBADARG.
+ *   beta            SMOOTH_L1_BETA, finite and >= 0; read by loss_type 0 only.
+ *   cls_agnostic    (ROI head) CLS_AGNOSTIC_BBOX_REG: the prediction row is [0,K] scores, [K+1,K+5) ONE delta
+ *                   quadruple shared by all classes (ld >= K + 5) instead of [K+1, K+1+4K) (ld >= 5K + 1).
+ * Per positive anchor / foreground row, with src the anchor / proposal, g the matched ground truth, d the deltas:
+ *   smooth-L1: t = get_deltas(src, g; weights), n = |d - t| per component.  beta < 1e-5: sum n, gradient sign(d - t)
+ *              (the L1 the default entry points compute); otherwise sum (n < beta ? 0.5 n^2 / beta : n - 0.5 beta),
+ *              gradient (d - t) / beta inside the quadratic zone, sign(d - t) outside.
+ *   GIoU:      p = apply_deltas(d, src; weights) with SCALE_CLAMP on dw / dh, not clipped to the image; eps = 1e-7;
+ *              I = overlap area (0 unless both extents > 0), U = area(p) + area(g) - I, C = enclosing area;
+ *              term = 1 - I / (U + eps) + (C - U) / (C + eps).  The gradient goes through apply_deltas and is exactly 0
+ *              for a dw / dh ABOVE the clamp (equal to it: passes, as torch.clamp).  At an exact tie of a max / min
+ *              between a predicted and a ground-truth coordinate the kernel takes the ground-truth side: the tied term
+ *              contributes no gradient (torch's autograd would give each side half).
+ * Normalisers are the default forms' (RPN: 1 / (batch_per_image * B); ROI: 1 / max(n_valid, 1)); value and gradient stay
+ * fused in one launch + the partial sum; no float atomics, bit-identical from run to run.  The default entry points are
+ * these calls with weights (1,1,1,1) / (10,10,5,5), loss_type 0, beta 0, cls_agnostic 0: one kernel body each, and --
+ * this file being built without fast-math and with -ffp-contract=off -- bit-identical to the literal-weight kernels. */
+int sfod_rpn_loss_opt(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
+                      int Wf, int stride, const int8_t* labels, const int32_t* matched,
+                      const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
+                      float* loss, const float* grad_scale, float* d_rpn_out, float* ws, float wx, float wy,
+                      float ww, float wh, int loss_type, float beta, void* stream);
 
 /* concat proposals and GT boxes: d2 add_ground_truth_to_proposals (roi_heads.py:170) */
 int sfod_append_gt(const float* props, const int32_t* prop_count, int B, int P,
@@ -456,6 +487,12 @@ int sfod_roi_align_bwd(const void* dout, int B, int H, int W, int C, const float
 int sfod_frcnn_loss(const float* pred, int ld, int R, int K, const float* rois,
                     const int32_t* gt_cls, const float* gt_box, const int32_t* n_valid,
                     float* loss, const float* grad_scale, float* d_pred, float* ws, void* stream);
+/* General form (options: see sfod_rpn_loss_opt).  cls_agnostic: the loss takes the row's single delta quadruple for every
+ * foreground row, whatever its class; rows that are not foreground get no box gradient. */
+int sfod_frcnn_loss_opt(const float* pred, int ld, int R, int K, const float* rois,
+                        const int32_t* gt_cls, const float* gt_box, const int32_t* n_valid,
+                        float* loss, const float* grad_scale, float* d_pred, float* ws, float wx, float wy,
+                        float ww, float wh, int loss_type, float beta, int cls_agnostic, void* stream);
 
 /* ---- K16: teacher inference post-processing (Appendix A.13; roi_heads.py:161) ----
  * step 1: softmax + per-class decode + clip + score filter -> candidates [B, P*K]
@@ -464,6 +501,13 @@ int sfod_frcnn_candidates(const float* pred, int ld, int B, int P, int K, const 
                           const int32_t* prop_count, const int32_t* image_sizes,
                           float score_thresh, float* cand_boxes, float* cand_scores,
                           int32_t* cand_count, void* stream);
+/* General form: transform weights by value; cls_agnostic: every class of a row decodes the same four deltas (the
+ * candidates stay [B, P*K]: K identical boxes with the K class scores). */
+int sfod_frcnn_candidates_opt(const float* pred, int ld, int B, int P, int K, const float* props,
+                              const int32_t* prop_count, const int32_t* image_sizes,
+                              float score_thresh, float* cand_boxes, float* cand_scores,
+                              int32_t* cand_count, float wx, float wy, float ww, float wh, int cls_agnostic,
+                              void* stream);
 /* d2 FastRCNNOutputLayers.predict_probs (reached from daod/modeling/roi_heads/source_free_fast_rcnn.py:16-17): row
  * softmax of scores [R, ld] (K+1 class scores per row) -> probs [R, K+1], in step 1's operation order. */
 int sfod_predict_probs(const float* scores, int ld, int R, int K, float* probs, void* stream);
@@ -494,6 +538,12 @@ int sfod_frcnn_finalize(const float* s_boxes, const float* sorted_scores, const 
 int sfod_bpc_loss(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,
                   int B, const int32_t* image_sizes, const float* gt_boxes, const int32_t* gt_classes,
                   const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws, void* stream);
+/* General form: transform weights by value; cls_agnostic: the gt-class decode and the K per-class decodes all read the
+ * row's single delta quadruple. */
+int sfod_bpc_loss_opt(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,
+                      int B, const int32_t* image_sizes, const float* gt_boxes, const int32_t* gt_classes,
+                      const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws, float wx, float wy,
+                      float ww, float wh, int cls_agnostic, void* stream);
 
 /* Class-wise adaptive pseudo-label threshold: AdaptiveConfidenceBasedSelfTrainingLoss
  * (daod/modeling/adaptive_thresh/adaptive_confidence.py:6-34, "convex" curve) with the trainer's bookkeeping

@@ -84,11 +84,99 @@ __device__ __forceinline__ Box clip_box(Box b, float h, float w) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Box-regression options (MODEL.{RPN,ROI_BOX_HEAD}.{BBOX_REG_WEIGHTS,BBOX_REG_LOSS_TYPE,SMOOTH_L1_BETA}): the
+// transform weights travel by value; with the defaults -- (1,1,1,1) / (10,10,5,5), smooth-L1, beta 0 -- every
+// expression below is the one the literal-weight kernels had (no fast-math, no contraction: a runtime 10.f rounds
+// like the literal), so the default entry points stay bit-identical.
+// ---------------------------------------------------------------------------------------------
+struct BoxWeights {
+  float x, y, w, h;
+};
+#define BOXREG_SMOOTH_L1 0
+#define BOXREG_GIOU 1
+#define GIOU_EPS 1e-7f
+
+static inline bool sfod_box_weights_ok(float wx, float wy, float ww, float wh) {
+  return isfinite(wx) && isfinite(wy) && isfinite(ww) && isfinite(wh) && wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f;
+}
+
+// Regression loss of ONE foreground box and, with `g`, its gradient with respect to the four predicted deltas `d`
+// (unscaled: the caller multiplies by normaliser and upstream gradient).  src: anchor / proposal, gt: matched box.
+//   smooth-L1: t = get_deltas(src, gt), n = |d - t|; beta < 1e-5: sum n (L1), gradient sign(d - t);
+//              else sum (n < beta ? 0.5 n^2 / beta : n - 0.5 beta), gradient (d - t) / beta inside, sign outside.
+//   GIoU     : p = apply_deltas(d, src) (SCALE_CLAMP on dw / dh, not clipped), fvcore giou_loss with eps 1e-7:
+//              1 - I / (U + eps) + (C - U) / (C + eps).  The gradient goes through apply_deltas; a dw / dh ABOVE the
+//              clamp has gradient exactly 0 (torch.clamp; at equality the gradient passes).  Ties of a max / min
+//              between a predicted and a ground-truth coordinate: the ground-truth side is taken (strict comparisons
+//              pick the predicted one), i.e. that term contributes no gradient; torch's autograd splits it in halves.
+__device__ __forceinline__ float box_reg_term(Box src, Box gt, const float* d, BoxWeights bw, int loss_type,
+                                              float beta, float* g) {
+  if (loss_type == BOXREG_GIOU) {
+    const float w = src.x2 - src.x1, h = src.y2 - src.y1;
+    const float dwr = d[2] / bw.w, dhr = d[3] / bw.h;
+    const Box p = apply_deltas(src, d[0], d[1], d[2], d[3], bw.x, bw.y, bw.w, bw.h);
+    const float pw = p.x2 - p.x1, ph = p.y2 - p.y1;
+    const float ap = pw * ph;
+    const float ag = (gt.x2 - gt.x1) * (gt.y2 - gt.y1);
+    const float iw = fminf(p.x2, gt.x2) - fmaxf(p.x1, gt.x1);
+    const float ih = fminf(p.y2, gt.y2) - fmaxf(p.y1, gt.y1);
+    const bool ov = iw > 0.f && ih > 0.f;
+    const float I = ov ? iw * ih : 0.f;
+    const float U = (ap + ag) - I;
+    const float cw = fmaxf(p.x2, gt.x2) - fminf(p.x1, gt.x1);
+    const float ch = fmaxf(p.y2, gt.y2) - fminf(p.y1, gt.y1);
+    const float C = cw * ch;
+    const float Ue = U + GIOU_EPS, Ce = C + GIOU_EPS;
+    const float loss = (1.f - I / Ue) + (C - U) / Ce;
+    if (g) {
+      // L(I, U(ap, I), C): dL/dI (total, U = ap + ag - I), dL/dap, dL/dC
+      const float gU = I / (Ue * Ue) - 1.f / Ce;
+      const float gI = -1.f / Ue - gU;
+      const float gC = Ue / (Ce * Ce);
+      float gx1 = -gU * ph, gx2 = gU * ph, gy1 = -gU * pw, gy2 = gU * pw;
+      if (ov) {
+        if (p.x2 < gt.x2) gx2 += gI * ih;
+        if (p.x1 > gt.x1) gx1 -= gI * ih;
+        if (p.y2 < gt.y2) gy2 += gI * iw;
+        if (p.y1 > gt.y1) gy1 -= gI * iw;
+      }
+      if (p.x2 > gt.x2) gx2 += gC * ch;
+      if (p.x1 < gt.x1) gx1 -= gC * ch;
+      if (p.y2 > gt.y2) gy2 += gC * cw;
+      if (p.y1 < gt.y1) gy1 -= gC * cw;
+      // x1 = pcx - pw / 2, x2 = pcx + pw / 2; pcx = d0 / wx * w + cx; pw = exp(min(d2 / ww, clamp)) * w
+      g[0] = (gx1 + gx2) * w / bw.x;
+      g[1] = (gy1 + gy2) * h / bw.y;
+      g[2] = dwr > SCALE_CLAMP ? 0.f : 0.5f * (gx2 - gx1) * pw / bw.w;
+      g[3] = dhr > SCALE_CLAMP ? 0.f : 0.5f * (gy2 - gy1) * ph / bw.h;
+    }
+    return loss;
+  }
+  float tg[4];
+  get_deltas(src, gt, bw.x, bw.y, bw.w, bw.h, tg);
+  float loss = 0.f;
+  const bool l1 = beta < 1e-5f;
+  for (int j = 0; j < 4; ++j) {
+    const float dd = d[j] - tg[j];
+    const float n = fabsf(dd);
+    const float sgn = (dd > 0.f) ? 1.f : ((dd < 0.f) ? -1.f : 0.f);
+    if (l1 || !(n < beta)) {
+      loss += l1 ? n : n - 0.5f * beta;
+      if (g) g[j] = sgn;
+    } else {
+      loss += 0.5f * n * n / beta;
+      if (g) g[j] = dd / beta;
+    }
+  }
+  return loss;
+}
+
+// ---------------------------------------------------------------------------------------------
 // RPN decode
 // ---------------------------------------------------------------------------------------------
 __global__ void k_rpn_decode(const float* __restrict__ rpn_out, int ld, const float* __restrict__ cell,
                              int A, int Hf, int Wf, int stride, const int32_t* __restrict__ sizes,
-                             float* __restrict__ props, float* __restrict__ scores, int32_t* flags) {
+                             float* __restrict__ props, float* __restrict__ scores, int32_t* flags, BoxWeights bw) {
   const int b = blockIdx.y;
   const int NA = Hf * Wf * A;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -98,7 +186,7 @@ __global__ void k_rpn_decode(const float* __restrict__ rpn_out, int ld, const fl
   const float logit = row[a];
   const float* d = row + A + a * 4;
   Box anc = anchor_at(cell, A, Wf, stride, i);
-  Box pb = apply_deltas(anc, d[0], d[1], d[2], d[3], 1.f, 1.f, 1.f, 1.f);
+  Box pb = apply_deltas(anc, d[0], d[1], d[2], d[3], bw.x, bw.y, bw.w, bw.h);
   bool fin = isfinite(pb.x1) && isfinite(pb.y1) && isfinite(pb.x2) && isfinite(pb.y2) && isfinite(logit);
   if (!fin) atomicOr(flags, 1);
   pb = clip_box(pb, (float)sizes[b * 2 + 0], (float)sizes[b * 2 + 1]);
@@ -106,10 +194,12 @@ __global__ void k_rpn_decode(const float* __restrict__ rpn_out, int ld, const fl
   scores[(int64_t)b * NA + i] = logit;
 }
 
-extern "C" int sfod_rpn_decode(const float* rpn_out, int ld, const float* cell_anchors, int A, int B,
-                               int Hf, int Wf, int stride, const int32_t* image_sizes, float* props,
-                               float* scores, int32_t* flags, void* stream) {
+extern "C" int sfod_rpn_decode_opt(const float* rpn_out, int ld, const float* cell_anchors, int A, int B,
+                                   int Hf, int Wf, int stride, const int32_t* image_sizes, float* props,
+                                   float* scores, int32_t* flags, float wx, float wy, float ww, float wh,
+                                   void* stream) {
   SFOD_REQUIRE_EXTENTS("rpn_decode", ld, A, B, Hf, Wf, stride);
+  SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "rpn_decode: box weights must be finite and > 0");
   SFOD_REQUIRE(sfod_prod_fits({Hf, Wf, A}) && sfod_prod_fits({5, A}) && sfod_prod_fits({B, Hf, Wf, ld}, 1LL << 40),
                "rpn_decode: oversized anchor grid");
   SFOD_REQUIRE(rpn_out && cell_anchors && image_sizes && props && scores && flags, "rpn_decode: null argument");
@@ -117,8 +207,15 @@ extern "C" int sfod_rpn_decode(const float* rpn_out, int ld, const float* cell_a
   const int NA = Hf * Wf * A;
   dim3 grid(cdiv(NA, 256), B);
   hipLaunchKernelGGL(k_rpn_decode, grid, dim3(256), 0, (hipStream_t)stream, rpn_out, ld, cell_anchors,
-                     A, Hf, Wf, stride, image_sizes, props, scores, flags);
+                     A, Hf, Wf, stride, image_sizes, props, scores, flags, BoxWeights{wx, wy, ww, wh});
   return sfod_check_launch("rpn_decode");
+}
+
+extern "C" int sfod_rpn_decode(const float* rpn_out, int ld, const float* cell_anchors, int A, int B,
+                               int Hf, int Wf, int stride, const int32_t* image_sizes, float* props,
+                               float* scores, int32_t* flags, void* stream) {
+  return sfod_rpn_decode_opt(rpn_out, ld, cell_anchors, A, B, Hf, Wf, stride, image_sizes, props, scores, flags,
+                             1.f, 1.f, 1.f, 1.f, stream);
 }
 
 __global__ void k_rpn_gather_topk(const float* __restrict__ props, const float* __restrict__ sscores,
@@ -887,7 +984,8 @@ __global__ void __launch_bounds__(256)
 k_rpn_loss(const float* __restrict__ rpn_out, int ld, const float* __restrict__ cell, int A, int Hf,
            int Wf, int stride, const int8_t* __restrict__ labels, const int32_t* __restrict__ matched,
            const float* __restrict__ gt, const int32_t* __restrict__ gt_count, int Gcap, float inv_norm,
-           const float* __restrict__ grad_scale, float* __restrict__ d_out, float* __restrict__ partial) {
+           const float* __restrict__ grad_scale, float* __restrict__ d_out, float* __restrict__ partial,
+           BoxWeights bw, int loss_type, float beta) {
   __shared__ float red[4];
   const int b = blockIdx.y;
   const int NA = Hf * Wf * A;
@@ -913,16 +1011,11 @@ k_rpn_loss(const float* __restrict__ rpn_out, int ld, const float* __restrict__ 
       Box t{0.f, 0.f, 0.f, 0.f};
       if (G > 0) t = load_box(gt + ((int64_t)b * Gcap + matched[(int64_t)b * NA + i]) * 4);
       Box anc = anchor_at(cell, A, Wf, stride, i);
-      float tg[4];
-      get_deltas(anc, t, 1.f, 1.f, 1.f, 1.f, tg);
-      for (int j = 0; j < 4; ++j) {
-        const float d = rpn_out[rowoff + A + a * 4 + j] - tg[j];
-        lloc += fabsf(d);
-        if (grad_scale) {
-          const float sgn = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
-          d_out[rowoff + A + a * 4 + j] = sgn * inv_norm * grad_scale[1];
-        }
-      }
+      float d[4], g[4];
+      for (int j = 0; j < 4; ++j) d[j] = rpn_out[rowoff + A + a * 4 + j];
+      lloc += box_reg_term(anc, t, d, bw, loss_type, beta, grad_scale ? g : nullptr);
+      if (grad_scale)
+        for (int j = 0; j < 4; ++j) d_out[rowoff + A + a * 4 + j] = g[j] * inv_norm * grad_scale[1];
     }
   }
   lcls = block_sum_f256(lcls, red);
@@ -954,12 +1047,16 @@ k_sum_partials2(const float* __restrict__ partial, int nblk, float scale0, float
   }
 }
 
-extern "C" int sfod_rpn_loss(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
-                             int Wf, int stride, const int8_t* labels, const int32_t* matched,
-                             const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
-                             float* loss, const float* grad_scale, float* d_rpn_out, float* ws,
-                             void* stream) {
+extern "C" int sfod_rpn_loss_opt(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
+                                 int Wf, int stride, const int8_t* labels, const int32_t* matched,
+                                 const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
+                                 float* loss, const float* grad_scale, float* d_rpn_out, float* ws, float wx,
+                                 float wy, float ww, float wh, int loss_type, float beta, void* stream) {
   SFOD_REQUIRE_EXTENTS("rpn_loss", ld, A, B, Hf, Wf, stride, Gcap, batch_per_image);
+  SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "rpn_loss: box weights must be finite and > 0");
+  SFOD_REQUIRE(loss_type == BOXREG_SMOOTH_L1 || loss_type == BOXREG_GIOU, "rpn_loss: loss_type must be 0 (smooth_l1) or 1 (giou)");
+  SFOD_REQUIRE(beta >= 0.f && isfinite(beta), "rpn_loss: beta must be finite and >= 0");
+  SFOD_REQUIRE(sfod_prod_fits({5, A}) && ld >= 5 * A, "rpn_loss: rpn_out leading dim < 5A");
   SFOD_REQUIRE(sfod_prod_fits({Hf, Wf, A}) && sfod_prod_fits({B, Hf, Wf, ld}, 1LL << 40) && sfod_prod_fits({batch_per_image, B}),
                "rpn_loss: oversized anchor grid");
   SFOD_REQUIRE(rpn_out && cell_anchors && labels && matched && gt_boxes && gt_count && loss && ws, "rpn_loss: null argument");
@@ -972,12 +1069,23 @@ extern "C" int sfod_rpn_loss(const float* rpn_out, int ld, const float* cell_anc
   }
   dim3 grid(cdiv(NA, 256), B);
   hipLaunchKernelGGL(k_rpn_loss, grid, dim3(256), 0, s, rpn_out, ld, cell_anchors, A, Hf, Wf, stride,
-                     labels, matched, gt_boxes, gt_count, Gcap, inv_norm, grad_scale, d_rpn_out, ws);
+                     labels, matched, gt_boxes, gt_count, Gcap, inv_norm, grad_scale, d_rpn_out, ws,
+                     BoxWeights{wx, wy, ww, wh}, loss_type, beta);
   int rc = sfod_check_launch("rpn_loss");
   if (rc) return rc;
   hipLaunchKernelGGL(k_sum_partials2, dim3(1), dim3(256), 0, s, ws, (int)(grid.x * grid.y), inv_norm,
                      inv_norm, (const int32_t*)nullptr, loss);
   return sfod_check_launch("rpn_loss_sum");
+}
+
+extern "C" int sfod_rpn_loss(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
+                             int Wf, int stride, const int8_t* labels, const int32_t* matched,
+                             const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
+                             float* loss, const float* grad_scale, float* d_rpn_out, float* ws,
+                             void* stream) {
+  return sfod_rpn_loss_opt(rpn_out, ld, cell_anchors, A, B, Hf, Wf, stride, labels, matched, gt_boxes, gt_count, Gcap,
+                           batch_per_image, loss, grad_scale, d_rpn_out, ws, 1.f, 1.f, 1.f, 1.f, BOXREG_SMOOTH_L1, 0.f,
+                           stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1085,7 +1193,8 @@ __global__ void __launch_bounds__(256)
 k_frcnn_loss(const float* __restrict__ pred, int ld, int R, int K, const float* __restrict__ rois,
              const int32_t* __restrict__ gt_cls, const float* __restrict__ gt_box,
              const int32_t* __restrict__ n_valid, const float* __restrict__ grad_scale,
-             float* __restrict__ d_pred, float* __restrict__ partial) {
+             float* __restrict__ d_pred, float* __restrict__ partial, BoxWeights bw, int loss_type, float beta,
+             int cls_agnostic) {
   __shared__ float red[4];
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   float lcls = 0.f, lbox = 0.f;
@@ -1112,14 +1221,13 @@ k_frcnn_loss(const float* __restrict__ pred, int ld, int R, int K, const float* 
         Box rb{rois[(int64_t)r * 5 + 1], rois[(int64_t)r * 5 + 2], rois[(int64_t)r * 5 + 3],
                rois[(int64_t)r * 5 + 4]};
         Box gb = load_box(gt_box + (int64_t)r * 4);
-        float tg[4];
-        get_deltas(rb, gb, 10.f, 10.f, 5.f, 5.f, tg);
         const float gs = grad_scale ? grad_scale[1] / fmaxf(nv, 1.f) : 0.f;
-        for (int j = 0; j < 4; ++j) {
-          const float d = row[K + 1 + c * 4 + j] - tg[j];
-          lbox += fabsf(d);
-          if (grad_scale) drow[K + 1 + c * 4 + j] = ((d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f)) * gs;
-        }
+        const int off = K + 1 + (cls_agnostic ? 0 : c * 4);
+        float d[4], g[4];
+        for (int j = 0; j < 4; ++j) d[j] = row[off + j];
+        lbox += box_reg_term(rb, gb, d, bw, loss_type, beta, grad_scale ? g : nullptr);
+        if (grad_scale)
+          for (int j = 0; j < 4; ++j) drow[off + j] = g[j] * gs;
       }
     }
   }
@@ -1128,14 +1236,18 @@ k_frcnn_loss(const float* __restrict__ pred, int ld, int R, int K, const float* 
   if (threadIdx.x == 0) { partial[blockIdx.x * 2] = lcls; partial[blockIdx.x * 2 + 1] = lbox; }
 }
 
-extern "C" int sfod_frcnn_loss(const float* pred, int ld, int R, int K, const float* rois,
-                               const int32_t* gt_cls, const float* gt_box, const int32_t* n_valid,
-                               float* loss, const float* grad_scale, float* d_pred, float* ws,
-                               void* stream) {
+extern "C" int sfod_frcnn_loss_opt(const float* pred, int ld, int R, int K, const float* rois,
+                                   const int32_t* gt_cls, const float* gt_box, const int32_t* n_valid,
+                                   float* loss, const float* grad_scale, float* d_pred, float* ws, float wx,
+                                   float wy, float ww, float wh, int loss_type, float beta, int cls_agnostic,
+                                   void* stream) {
   SFOD_REQUIRE_EXTENTS("frcnn_loss", ld, R, K);
   // (no per-thread class array here, unlike the candidates kernel: K is bounded by the row only -- Detectron2's default 80
   // classes run through it in tests/test_gpu_d2_golden.py)
-  SFOD_REQUIRE(K >= 1 && K <= 4096 && ld >= 5 * K + 1, "frcnn_loss K / ld");
+  SFOD_REQUIRE(K >= 1 && K <= 4096 && ld >= (cls_agnostic ? K + 5 : 5 * K + 1), "frcnn_loss K / ld");
+  SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "frcnn_loss: box weights must be finite and > 0");
+  SFOD_REQUIRE(loss_type == BOXREG_SMOOTH_L1 || loss_type == BOXREG_GIOU, "frcnn_loss: loss_type must be 0 (smooth_l1) or 1 (giou)");
+  SFOD_REQUIRE(beta >= 0.f && isfinite(beta), "frcnn_loss: beta must be finite and >= 0");
   hipStream_t s = (hipStream_t)stream;
   if (grad_scale) {
     SFOD_REQUIRE(d_pred != nullptr, "d_pred");
@@ -1143,11 +1255,19 @@ extern "C" int sfod_frcnn_loss(const float* pred, int ld, int R, int K, const fl
   }
   const int nblk = cdiv(R, 256);
   hipLaunchKernelGGL(k_frcnn_loss, dim3(nblk), dim3(256), 0, s, pred, ld, R, K, rois, gt_cls, gt_box,
-                     n_valid, grad_scale, d_pred, ws);
+                     n_valid, grad_scale, d_pred, ws, BoxWeights{wx, wy, ww, wh}, loss_type, beta, cls_agnostic != 0);
   int rc = sfod_check_launch("frcnn_loss");
   if (rc) return rc;
   hipLaunchKernelGGL(k_sum_partials2, dim3(1), dim3(256), 0, s, ws, nblk, 1.f, 1.f, n_valid, loss);
   return sfod_check_launch("frcnn_loss_sum");
+}
+
+extern "C" int sfod_frcnn_loss(const float* pred, int ld, int R, int K, const float* rois,
+                               const int32_t* gt_cls, const float* gt_box, const int32_t* n_valid,
+                               float* loss, const float* grad_scale, float* d_pred, float* ws,
+                               void* stream) {
+  return sfod_frcnn_loss_opt(pred, ld, R, K, rois, gt_cls, gt_box, n_valid, loss, grad_scale, d_pred, ws, 10.f, 10.f,
+                             5.f, 5.f, BOXREG_SMOOTH_L1, 0.f, 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1156,7 +1276,8 @@ extern "C" int sfod_frcnn_loss(const float* pred, int ld, int R, int K, const fl
 __global__ void __launch_bounds__(256)
 k_frcnn_candidates(const float* __restrict__ pred, int ld, int P, int K, const float* __restrict__ props,
                    const int32_t* __restrict__ pc, const int32_t* __restrict__ sizes, float thr,
-                   float* __restrict__ cboxes, float* __restrict__ cscores, int32_t* ccount) {
+                   float* __restrict__ cboxes, float* __restrict__ cscores, int32_t* ccount, BoxWeights bw,
+                   int cls_agnostic) {
   const int b = blockIdx.y;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   int npass = 0;
@@ -1175,8 +1296,8 @@ k_frcnn_candidates(const float* __restrict__ pred, int ld, int P, int K, const f
       for (int c = 0; c <= K; ++c) { prob[c] = prob[c] / ssum; fin = fin && isfinite(prob[c]); }
       Box pb = load_box(props + r * 4);
       for (int c = 0; c < K; ++c) {
-        const float* d = row + K + 1 + c * 4;
-        bx[c] = apply_deltas(pb, d[0], d[1], d[2], d[3], 10.f, 10.f, 5.f, 5.f);
+        const float* d = row + K + 1 + (cls_agnostic ? 0 : c * 4);     // class-agnostic: every class decodes to the same box
+        bx[c] = apply_deltas(pb, d[0], d[1], d[2], d[3], bw.x, bw.y, bw.w, bw.h);
         fin = fin && isfinite(bx[c].x1) && isfinite(bx[c].y1) && isfinite(bx[c].x2) && isfinite(bx[c].y2);
       }
     }
@@ -1194,18 +1315,29 @@ k_frcnn_candidates(const float* __restrict__ pred, int ld, int P, int K, const f
   if ((threadIdx.x & 63) == 0 && npass) atomicAdd(ccount + b, npass);
 }
 
-extern "C" int sfod_frcnn_candidates(const float* pred, int ld, int B, int P, int K, const float* props,
-                                     const int32_t* prop_count, const int32_t* image_sizes,
-                                     float score_thresh, float* cand_boxes, float* cand_scores,
-                                     int32_t* cand_count, void* stream) {
+extern "C" int sfod_frcnn_candidates_opt(const float* pred, int ld, int B, int P, int K, const float* props,
+                                         const int32_t* prop_count, const int32_t* image_sizes,
+                                         float score_thresh, float* cand_boxes, float* cand_scores,
+                                         int32_t* cand_count, float wx, float wy, float ww, float wh,
+                                         int cls_agnostic, void* stream) {
   SFOD_REQUIRE_EXTENTS("frcnn_candidates", ld, B, P, K);
-  SFOD_REQUIRE(K <= KMAX && ld >= 5 * K + 1, "frcnn_candidates K / ld");
+  SFOD_REQUIRE(K <= KMAX && ld >= (cls_agnostic ? K + 5 : 5 * K + 1), "frcnn_candidates K / ld");
+  SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "frcnn_candidates: box weights must be finite and > 0");
   hipStream_t s = (hipStream_t)stream;
   (void)hipMemsetAsync(cand_count, 0, sizeof(int32_t) * B, s);
   dim3 grid(cdiv(P, 256), B);
   hipLaunchKernelGGL(k_frcnn_candidates, grid, dim3(256), 0, s, pred, ld, P, K, props, prop_count,
-                     image_sizes, score_thresh, cand_boxes, cand_scores, cand_count);
+                     image_sizes, score_thresh, cand_boxes, cand_scores, cand_count, BoxWeights{wx, wy, ww, wh},
+                     cls_agnostic != 0);
   return sfod_check_launch("frcnn_candidates");
+}
+
+extern "C" int sfod_frcnn_candidates(const float* pred, int ld, int B, int P, int K, const float* props,
+                                     const int32_t* prop_count, const int32_t* image_sizes,
+                                     float score_thresh, float* cand_boxes, float* cand_scores,
+                                     int32_t* cand_count, void* stream) {
+  return sfod_frcnn_candidates_opt(pred, ld, B, P, K, props, prop_count, image_sizes, score_thresh, cand_boxes,
+                                   cand_scores, cand_count, 10.f, 10.f, 5.f, 5.f, 0, stream);
 }
 
 // FastRCNNOutputLayers.predict_probs (d2; reached from source_free_fast_rcnn.py:16-17 convert_bbox_scores): the row
@@ -1346,7 +1478,8 @@ __global__ void __launch_bounds__(256)
 k_bpc_sums(const float* __restrict__ pred, int ld, int R, int K, const float* __restrict__ rois,
            const int32_t* __restrict__ roi_cls, const int32_t* __restrict__ sizes,
            const float* __restrict__ gboxes, const int32_t* __restrict__ gcls,
-           const int32_t* __restrict__ gcount, int B, int G, float iou_thr, double* __restrict__ sums) {
+           const int32_t* __restrict__ gcount, int B, int G, float iou_thr, double* __restrict__ sums,
+           BoxWeights bw, int cls_agnostic) {
   // one thread per (sampled row, class); the row's softmax and finite test are recomputed by its K threads
   // (registers only: no per-thread class arrays)
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1368,12 +1501,12 @@ k_bpc_sums(const float* __restrict__ pred, int ld, int R, int K, const float* __
     for (int k = 0; k <= K; ++k) fin = fin && isfinite(expf(row[k] - m) / ssum);
     const float sc = expf(row[c] - m) / ssum;
     const int gtc = min(max(roi_cls[r], 0), K - 1);
-    const float* dg = row + K + 1 + gtc * 4;
-    const Box pb = apply_deltas(Box{roi[1], roi[2], roi[3], roi[4]}, dg[0], dg[1], dg[2], dg[3], 10.f, 10.f, 5.f, 5.f);
+    const float* dg = row + K + 1 + (cls_agnostic ? 0 : gtc * 4);
+    const Box pb = apply_deltas(Box{roi[1], roi[2], roi[3], roi[4]}, dg[0], dg[1], dg[2], dg[3], bw.x, bw.y, bw.w, bw.h);
     Box mine{0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < K; ++k) {
-      const float* d = row + K + 1 + k * 4;
-      const Box x = apply_deltas(pb, d[0], d[1], d[2], d[3], 10.f, 10.f, 5.f, 5.f);
+      const float* d = row + K + 1 + (cls_agnostic ? 0 : k * 4);
+      const Box x = apply_deltas(pb, d[0], d[1], d[2], d[3], bw.x, bw.y, bw.w, bw.h);
       fin = fin && isfinite(x.x1) && isfinite(x.y1) && isfinite(x.x2) && isfinite(x.y2);
       if (k == c) mine = x;
     }
@@ -1434,22 +1567,32 @@ __global__ void k_bpc_final(const double* __restrict__ sums, int B, float* __res
   out[0] = n ? tot / (float)n : 0.f;
 }
 
-extern "C" int sfod_bpc_loss(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,
-                             int B, const int32_t* image_sizes, const float* gt_boxes, const int32_t* gt_classes,
-                             const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws,
-                             void* stream) {
+extern "C" int sfod_bpc_loss_opt(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,
+                                 int B, const int32_t* image_sizes, const float* gt_boxes, const int32_t* gt_classes,
+                                 const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws, float wx,
+                                 float wy, float ww, float wh, int cls_agnostic, void* stream) {
   SFOD_REQUIRE_EXTENTS("bpc_loss", ld, R, K, B, G);
-  SFOD_REQUIRE(K >= 1 && K <= KMAX && ld >= 5 * K + 1, "bpc_loss K / ld");
+  SFOD_REQUIRE(K >= 1 && K <= KMAX && ld >= (cls_agnostic ? K + 5 : 5 * K + 1), "bpc_loss K / ld");
+  SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "bpc_loss: box weights must be finite and > 0");
   hipStream_t s = (hipStream_t)stream;
   if (B > 0) (void)hipMemsetAsync(ws, 0, sizeof(double) * 4 * B, s);
   if (B > 0 && R > 0) {
     hipLaunchKernelGGL(k_bpc_sums, dim3(cdiv((int64_t)R * K, 256)), dim3(256), 0, s, pred, ld, R, K, rois, roi_cls,
-                       image_sizes, gt_boxes, gt_classes, gt_count, B, G, iou_thresh, (double*)ws);
+                       image_sizes, gt_boxes, gt_classes, gt_count, B, G, iou_thresh, (double*)ws,
+                       BoxWeights{wx, wy, ww, wh}, cls_agnostic != 0);
   }
   int rc = sfod_check_launch("bpc_sums");
   if (rc) return rc;
   hipLaunchKernelGGL(k_bpc_final, dim3(1), dim3(64), 0, s, (const double*)ws, B, loss);
   return sfod_check_launch("bpc_final");
+}
+
+extern "C" int sfod_bpc_loss(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,
+                             int B, const int32_t* image_sizes, const float* gt_boxes, const int32_t* gt_classes,
+                             const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws,
+                             void* stream) {
+  return sfod_bpc_loss_opt(pred, ld, R, K, rois, roi_cls, B, image_sizes, gt_boxes, gt_classes, gt_count, G, iou_thresh,
+                           loss, ws, 10.f, 10.f, 5.f, 5.f, 0, stream);
 }
 
 // Class-wise adaptive pseudo-label threshold (adaptive_thresh/adaptive_confidence.py:6-34 and the trainer's

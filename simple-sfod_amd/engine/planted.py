@@ -18,6 +18,10 @@ BIAS_BRACKET = (-40.0, 40.0)
 
 
 def spread_class_logits(box_predictor, scale):
+    if getattr(box_predictor, "cls_agnostic_bbox_reg", False):
+        # the calibration (scales, target band, the oracle gates that share it) was made on per-class box predictors
+        raise ValueError("MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG must be False for planted labels (the benchmark's "
+                         "calibration), got True")
     with torch.no_grad():
         box_predictor.cls_score.weight.mul_(scale)
 

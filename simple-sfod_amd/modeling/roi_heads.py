@@ -20,6 +20,7 @@ from ..registry import ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY
 from ..structures import Boxes, Instances, ShapeSpec
 from .offchain import OffChain as _OffChain
 from .batched import BatchedDetections, BatchedGT, BatchedProposals
+from .box_regression import ROI_DEFAULT_WEIGHTS, roi_box_reg_options
 
 
 class ROIPooler(nn.Module):
@@ -68,15 +69,18 @@ class FastRCNNOutputLayers(nn.Module):
         super().__init__()
         d = input_shape.channels
         self.num_classes = cfg.MODEL.ROI_HEADS.NUM_CLASSES
-        assert not cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG
+        # BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA / BBOX_REG_WEIGHTS / CLS_AGNOSTIC_BBOX_REG / BBOX_REG_LOSS_WEIGHT (ValueError
+        # naming the key for what is not built); ``_box_reg`` is what the native calls take: None = the default entry points
+        self.box_reg, self.box_reg_loss_weight = roi_box_reg_options(cfg)
+        self.box_reg_loss_type, self.smooth_l1_beta = self.box_reg.loss_type, self.box_reg.beta
+        self.box_reg_weights, self.cls_agnostic_bbox_reg = self.box_reg.weights, self.box_reg.cls_agnostic
+        self._box_reg = None if self.box_reg.is_default(ROI_DEFAULT_WEIGHTS) else self.box_reg
         self.cls_score = nn.Linear(d, self.num_classes + 1)
-        self.bbox_pred = nn.Linear(d, self.num_classes * 4)
+        self.bbox_pred = nn.Linear(d, 4 if self.cls_agnostic_bbox_reg else self.num_classes * 4)
         nn.init.normal_(self.cls_score.weight, std=0.01)
         nn.init.normal_(self.bbox_pred.weight, std=0.001)
         for l in [self.cls_score, self.bbox_pred]:
             nn.init.constant_(l.bias, 0)
-        assert tuple(cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS) == (10.0, 10.0, 5.0, 5.0)
-        assert cfg.MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA == 0.0
         self.test_score_thresh = cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST
         self.test_nms_thresh = cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST
         self.test_topk_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
@@ -85,7 +89,7 @@ class FastRCNNOutputLayers(nn.Module):
 _SCALE_CLAMP = math.log(1000.0 / 16)
 
 
-def _apply_deltas(deltas, boxes, weights=(10.0, 10.0, 5.0, 5.0)):
+def _apply_deltas(deltas, boxes, weights=ROI_DEFAULT_WEIGHTS):
     """d2 Box2BoxTransform.apply_deltas (A.5) in torch ops: the Instances-level API twins below use it; the
     step itself decodes inside the HIP kernels (detect.hip)."""
     deltas, boxes = deltas.float(), boxes.float()
@@ -102,14 +106,15 @@ def _apply_deltas(deltas, boxes, weights=(10.0, 10.0, 5.0, 5.0)):
 
 class _PredictorAPI:
     """d2 ``FastRCNNOutputLayers.{predict_boxes, predict_probs, predict_boxes_for_gt_classes}`` on
-    ``predictions = (scores [R,K+1], proposal_deltas [R,4K])`` and ``list[Instances]`` proposals (A.12)."""
+    ``predictions = (scores [R,K+1], proposal_deltas [R,4K] or, class-agnostic, [R,4])`` and ``list[Instances]``
+    proposals (A.12), under the configured BBOX_REG_WEIGHTS."""
 
     def predict_boxes(self, predictions, proposals):
         _, deltas = predictions
         if not len(proposals):
             return []
         pb = torch.cat([p.proposal_boxes.tensor for p in proposals], dim=0)
-        return _apply_deltas(deltas, pb).split([len(p) for p in proposals])
+        return _apply_deltas(deltas, pb, self.box_reg_weights).split([len(p) for p in proposals])
 
     def predict_probs(self, predictions, proposals):
         scores, _ = predictions
@@ -122,7 +127,7 @@ class _PredictorAPI:
         _, deltas = predictions
         pb = torch.cat([p.proposal_boxes.tensor for p in proposals], dim=0)
         N, K = pb.shape[0], deltas.shape[1] // 4
-        boxes = _apply_deltas(deltas, pb)
+        boxes = _apply_deltas(deltas, pb, self.box_reg_weights)
         if K > 1:
             gt = torch.cat([p.gt_classes for p in proposals], dim=0).clamp(0, K - 1)
             boxes = boxes.view(N, K, 4)[torch.arange(N, device=boxes.device), gt]
@@ -189,7 +194,7 @@ class InstanceProposals:
         sizes = native.dev_const(tuple((int(s[0]), int(s[1])) for s in sm["image_sizes"]), torch.int32,
                                  self.pred.device)
         return native.bpc_loss(self.pred, h.num_classes, sm["rois"], sm["gt_cls"], sizes, targets.boxes,
-                               targets.classes, targets.count, iou_thresh)
+                               targets.classes, targets.count, iou_thresh, box_reg=h.box_predictor._box_reg)
 
     def to_instances(self):
         h, sm = self.heads, self.samples
@@ -203,8 +208,8 @@ class InstanceProposals:
             p.gt_classes = cls[m].long()
             props.append(p)
         order = torch.cat([torch.nonzero(rois[:, 0] == b).flatten() for b in range(len(props))])
-        predictions = (self.pred[order, : K + 1], self.pred[order, K + 1: 5 * K + 1])
         bp = h.box_predictor
+        predictions = (self.pred[order, : K + 1], self.pred[order, K + 1: bp.box_reg.pred_cols(K)])
         for p, nb in zip(props, bp.predict_boxes_for_gt_classes(predictions, props)):     # :136-143
             p.proposal_boxes = Boxes(nb)
         return bp.convert_bbox_scores(predictions, props)[0]
@@ -216,19 +221,26 @@ class _ROILossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, heads, feat_nchw, samples, *params):
         st = heads._box_forward(feat_nchw, samples["rois"])
+        bp = heads.box_predictor
         loss, _ = native.frcnn_loss(st["pred"], heads.num_classes, samples["rois"], samples["gt_cls"],
-                                    samples["gt_box"], samples["n_valid"])
+                                    samples["gt_box"], samples["n_valid"], box_reg=bp._box_reg)
         ctx.heads, ctx.st, ctx.samples = heads, st, samples
         ctx.feat_shape = feat_nchw.shape
         heads._last_pred = st["pred"]          # for InstanceProposals (BPC); alive until the backward anyway
-        return loss[0].clone(), loss[1].clone()
+        # BBOX_REG_LOSS_WEIGHT: applied here, an fp32 scalar multiplication like the ``loss * weight`` it replaces (1.0: the
+        # node returns what it returned before the key was read)
+        ctx.box_w = bp.box_reg_loss_weight
+        return loss[0].clone(), (loss[1].clone() if ctx.box_w == 1.0 else loss[1] * ctx.box_w)
 
     @staticmethod
     def backward(ctx, g_cls, g_box):
         heads, st, samples = ctx.heads, ctx.st, ctx.samples
+        if ctx.box_w != 1.0:
+            g_box = g_box * ctx.box_w
         gs = torch.stack([g_cls.reshape(()), g_box.reshape(())]).float().contiguous()
         _, d_pred = native.frcnn_loss(st["pred"], heads.num_classes, samples["rois"], samples["gt_cls"],
-                                      samples["gt_box"], samples["n_valid"], grad_scale=gs)
+                                      samples["gt_box"], samples["n_valid"], grad_scale=gs,
+                                      box_reg=heads.box_predictor._box_reg)
         dfeat, pgrads = heads._box_backward(st, samples["rois"], d_pred, ctx.feat_shape)
         ctx.st = None
         return (None, dfeat, None) + tuple(pgrads)
@@ -258,7 +270,8 @@ class StandardROIHeads(nn.Module):
         self.channels = shape.channels
         self.compute_dtype = native.mode_dtype(cfg.SFOD.COMPUTE_DTYPE)
         K = self.num_classes
-        self.pred_ld = (5 * K + 1 + 7) // 8 * 8
+        self.pred_cols = self.box_predictor.box_reg.pred_cols(K)      # K + 1 scores | 4K deltas (class-agnostic: 4)
+        self.pred_ld = (self.pred_cols + 7) // 8 * 8
         self.bbox_threshold = cfg.SEMISUPNET.BBOX_THRESHOLD if "SEMISUPNET" in cfg else 0.7
         self.nms_numel_limit = 20000  # torchvision batched_nms switch for GPU tensors (A.6)
         self.train_on_pred_boxes = cfg.MODEL.ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES
@@ -322,7 +335,7 @@ class StandardROIHeads(nn.Module):
         dt = native.dt_of_dtype(dtype)
         bh = self.box_head
         K = self.num_classes
-        NP = 5 * K + 1
+        NP = self.pred_cols
         d_pred_c = native.cast(d_pred, dtype)
         # predictor: its parameter gradients beside the data-gradient path (``_OffChain``), like fc2's and fc1's below
         off = _OffChain(self, d_pred.is_cuda)
@@ -412,7 +425,7 @@ class StandardROIHeads(nn.Module):
                                          feat.device)
         out = native.frcnn_inference(st["pred"], self.num_classes, proposals.boxes, proposals.count, sizes_dev,
                                      bp.test_score_thresh, bp.test_nms_thresh, bp.test_topk_per_image,
-                                     self.bbox_threshold, self.nms_numel_limit)
+                                     self.bbox_threshold, self.nms_numel_limit, box_reg=bp._box_reg)
         return BatchedDetections(out, proposals.image_sizes), st["pred"]
 
     # ---- module surface (roi_heads.py:68-106) -------------------------------------------------------

@@ -17,6 +17,7 @@ import torch.nn as nn
 from .. import native
 from ..registry import PROPOSAL_GENERATOR_REGISTRY
 from .batched import BatchedGT, BatchedProposals
+from .box_regression import RPN_DEFAULT_WEIGHTS, rpn_box_reg_options
 from .offchain import OffChain, take_loss_grads_ready
 
 
@@ -151,8 +152,14 @@ class RPN(nn.Module):
         self.batch_size_per_image = r.BATCH_SIZE_PER_IMAGE
         self.positive_fraction = r.POSITIVE_FRACTION
         self.iou_thresholds = list(r.IOU_THRESHOLDS)
-        assert list(r.IOU_LABELS) == [0, -1, 1] and r.BBOX_REG_LOSS_TYPE == "smooth_l1" and r.SMOOTH_L1_BETA == 0.0
-        assert tuple(r.BBOX_REG_WEIGHTS) == (1.0, 1.0, 1.0, 1.0)
+        if list(r.IOU_LABELS) != [0, -1, 1]:
+            raise ValueError(f"MODEL.RPN.IOU_LABELS must be [0, -1, 1], got {list(r.IOU_LABELS)!r}")
+        # BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA / BBOX_REG_WEIGHTS (ValueError naming the key for what is not built);
+        # ``_box_reg`` is what the native calls take: None = the default entry points, as before these keys were read
+        self.box_reg = rpn_box_reg_options(cfg)
+        self.box_reg_loss_type, self.smooth_l1_beta = self.box_reg.loss_type, self.box_reg.beta
+        self.box_reg_weights = self.box_reg.weights
+        self._box_reg = None if self.box_reg.is_default(RPN_DEFAULT_WEIGHTS) else self.box_reg
         self.pre_nms_topk = {True: r.PRE_NMS_TOPK_TRAIN, False: r.PRE_NMS_TOPK_TEST}
         self.post_nms_topk = {True: r.POST_NMS_TOPK_TRAIN, False: r.POST_NMS_TOPK_TEST}
         self.nms_thresh = r.NMS_THRESH
@@ -217,7 +224,8 @@ class RPN(nn.Module):
             self._flags = torch.zeros(1, dtype=torch.int32, device=dev)
         if sizes_dev is None:
             sizes_dev = self._sizes_dev(image_sizes, dev)
-        props, scores = native.rpn_decode(st["rpn_out"], self._cell(), B, Hf, Wf, self.stride, sizes_dev, self._flags)
+        props, scores = native.rpn_decode(st["rpn_out"], self._cell(), B, Hf, Wf, self.stride, sizes_dev, self._flags,
+                                          box_reg=self._box_reg)
         ss, si = native.segmented_sort_desc(scores)
         NA = scores.shape[1]
         k = min(self.pre_nms_topk[self.training], NA)
@@ -241,7 +249,7 @@ class RPN(nn.Module):
         matched, labels = native.anchor_match(cell, B, Hf, Wf, self.stride, gt.boxes, gt.count, lo, hi)
         native.subsample_rpn_(labels, keys, self.batch_size_per_image, self.positive_fraction)
         loss, _ = native.rpn_loss(st["rpn_out"], cell, B, Hf, Wf, self.stride, labels, matched, gt.boxes,
-                                  gt.count, self.batch_size_per_image)
+                                  gt.count, self.batch_size_per_image, box_reg=self._box_reg)
         return loss, (labels, matched)
 
     def _loss_backward(self, st, lab_state, gt, grad_scale):
@@ -252,7 +260,7 @@ class RPN(nn.Module):
         dtype = native.grad_dtype_of(self.compute_dtype)      # operands of the backward products ("f16x3": bf16 pairs)
         dt = native.dt_of_dtype(dtype)
         _, d_out = native.rpn_loss(st["rpn_out"], cell, B, Hf, Wf, self.stride, labels, matched, gt.boxes,
-                                   gt.count, self.batch_size_per_image, grad_scale=grad_scale)
+                                   gt.count, self.batch_size_per_image, grad_scale=grad_scale, box_reg=self._box_reg)
         M = B * Hf * Wf
         t2 = st["t"].view(M, C)
         d_out_c = native.cast(d_out, dtype)

@@ -1009,12 +1009,43 @@ def cast(src, dtype):
 
 
 # ---- detection ops -----------------------------------------------------------------------------
-def rpn_decode(rpn_out, cell, B, Hf, Wf, stride, sizes, flags):
+BOX_REG_LOSS_TYPES = {"smooth_l1": 0, "giou": 1}      # loss_type of the ``*_opt`` entry points (include/sfod_hip.h)
+
+
+class BoxRegOptions:
+    """Box-regression options of one head, as the ``sfod_*_opt`` entry points take them: Box2BoxTransform ``weights``
+    (wx, wy, ww, wh), ``loss_type`` ("smooth_l1" / "giou"), smooth-L1 ``beta`` and, for the ROI head, ``cls_agnostic``
+    (one delta quadruple per row).  The wrappers below take ``box_reg=None`` for the default entry points and an instance
+    for the general forms (which, given the default values, compute the same bits)."""
+    __slots__ = ("weights", "loss_type", "beta", "cls_agnostic")
+
+    def __init__(self, weights, loss_type="smooth_l1", beta=0.0, cls_agnostic=False):
+        self.weights = tuple(float(w) for w in weights)
+        assert len(self.weights) == 4
+        self.loss_type, self.beta, self.cls_agnostic = str(loss_type), float(beta), bool(cls_agnostic)
+
+    def is_default(self, weights):
+        return (self.weights == tuple(float(w) for w in weights) and self.loss_type == "smooth_l1" and self.beta == 0.0
+                and not self.cls_agnostic)
+
+    def pred_cols(self, K):
+        """columns of a Fast R-CNN prediction row: K + 1 scores and 4 (class-agnostic) or 4K deltas"""
+        return K + 5 if self.cls_agnostic else 5 * K + 1
+
+    def __repr__(self):
+        return f"BoxRegOptions({self.weights}, {self.loss_type!r}, beta={self.beta}, cls_agnostic={self.cls_agnostic})"
+
+
+def rpn_decode(rpn_out, cell, B, Hf, Wf, stride, sizes, flags, box_reg=None):
     A = cell.shape[0]
     NA = Hf * Wf * A
     props = torch.empty(B, NA, 4, dtype=torch.float32, device=rpn_out.device)
     scores = torch.empty(B, NA, dtype=torch.float32, device=rpn_out.device)
-    call("sfod_rpn_decode", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, sizes, props, scores, flags)
+    if box_reg is None:
+        call("sfod_rpn_decode", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, sizes, props, scores, flags)
+    else:
+        call("sfod_rpn_decode_opt", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, sizes, props, scores, flags,
+             *box_reg.weights)
     return props, scores
 
 
@@ -1112,7 +1143,7 @@ def subsample_roi(cls, keys, num, pos_frac, bg_label):
 
 
 def rpn_loss(rpn_out, cell, B, Hf, Wf, stride, labels, matched, gt_boxes, gt_count, batch_per_image,
-             grad_scale=None):
+             grad_scale=None, box_reg=None):
     A = cell.shape[0]
     NA = Hf * Wf * A
     dev = rpn_out.device
@@ -1120,8 +1151,13 @@ def rpn_loss(rpn_out, cell, B, Hf, Wf, stride, labels, matched, gt_boxes, gt_cou
     nblk = (NA + 255) // 256 * B
     ws = torch.empty(nblk * 2, dtype=torch.float32, device=dev)
     d_out = torch.empty_like(rpn_out) if grad_scale is not None else None
-    call("sfod_rpn_loss", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, labels, matched, gt_boxes,
-         gt_count, gt_boxes.shape[1], batch_per_image, loss, grad_scale, d_out, ws)
+    if box_reg is None:
+        call("sfod_rpn_loss", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, labels, matched, gt_boxes,
+             gt_count, gt_boxes.shape[1], batch_per_image, loss, grad_scale, d_out, ws)
+    else:
+        call("sfod_rpn_loss_opt", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, labels, matched, gt_boxes,
+             gt_count, gt_boxes.shape[1], batch_per_image, loss, grad_scale, d_out, ws, *box_reg.weights,
+             BOX_REG_LOSS_TYPES[box_reg.loss_type], box_reg.beta)
     return loss, d_out
 
 
@@ -1170,18 +1206,22 @@ def roi_align_bwd(dout, rois, feat_shape, pooled, scale, dfeat=None):
     return dfeat
 
 
-def frcnn_loss(pred, K, rois, gt_cls, gt_box, n_valid, grad_scale=None):
+def frcnn_loss(pred, K, rois, gt_cls, gt_box, n_valid, grad_scale=None, box_reg=None):
     R, ld = pred.shape
     dev = pred.device
     loss = torch.empty(2, dtype=torch.float32, device=dev)
     ws = torch.empty(((R + 255) // 256) * 2, dtype=torch.float32, device=dev)
     d_pred = torch.empty_like(pred) if grad_scale is not None else None
-    call("sfod_frcnn_loss", pred, ld, R, K, rois, gt_cls, gt_box, n_valid, loss, grad_scale, d_pred, ws)
+    if box_reg is None:
+        call("sfod_frcnn_loss", pred, ld, R, K, rois, gt_cls, gt_box, n_valid, loss, grad_scale, d_pred, ws)
+    else:
+        call("sfod_frcnn_loss_opt", pred, ld, R, K, rois, gt_cls, gt_box, n_valid, loss, grad_scale, d_pred, ws,
+             *box_reg.weights, BOX_REG_LOSS_TYPES[box_reg.loss_type], box_reg.beta, int(box_reg.cls_agnostic))
     return loss, d_pred
 
 
 def frcnn_inference(pred, K, props, prop_count, sizes, score_thresh, nms_thresh, max_det, pseudo_thr,
-                    numel_limit=20000):
+                    numel_limit=20000, box_reg=None):
     """Teacher post-processing -> dict of fixed-capacity per-image arrays + counts."""
     B, P, _ = props.shape
     dev = pred.device
@@ -1189,8 +1229,12 @@ def frcnn_inference(pred, K, props, prop_count, sizes, score_thresh, nms_thresh,
     cb = torch.empty(B, n, 4, dtype=torch.float32, device=dev)
     cs = torch.empty(B, n, dtype=torch.float32, device=dev)
     cc = torch.empty(B, dtype=torch.int32, device=dev)
-    call("sfod_frcnn_candidates", pred, pred.shape[-1], B, P, K, props, prop_count, sizes, float(score_thresh),
-         cb, cs, cc)
+    if box_reg is None:
+        call("sfod_frcnn_candidates", pred, pred.shape[-1], B, P, K, props, prop_count, sizes, float(score_thresh),
+             cb, cs, cc)
+    else:
+        call("sfod_frcnn_candidates_opt", pred, pred.shape[-1], B, P, K, props, prop_count, sizes, float(score_thresh),
+             cb, cs, cc, *box_reg.weights, int(box_reg.cls_agnostic))
     ss, si = segmented_sort_desc(cs)
     sb = torch.empty(B, n, 4, dtype=torch.float32, device=dev)
     sa = torch.empty(B, n, 4, dtype=torch.float32, device=dev)
@@ -1215,13 +1259,17 @@ def frcnn_inference(pred, K, props, prop_count, sizes, score_thresh, nms_thresh,
     return out
 
 
-def bpc_loss(pred, K, rois, roi_cls, sizes_dev, gt_boxes, gt_classes, gt_count, iou_thresh=0.5):
+def bpc_loss(pred, K, rois, roi_cls, sizes_dev, gt_boxes, gt_classes, gt_count, iou_thresh=0.5, box_reg=None):
     """BPC calibration scalar of one training pass (fused convert_bbox_scores + bpc_loss) -> 0-dim tensor."""
     B, G = gt_classes.shape
     loss = torch.empty(1, dtype=torch.float32, device=pred.device)
     ws = torch.empty(max(B, 1) * 4, dtype=torch.float64, device=pred.device)
-    call("sfod_bpc_loss", pred, pred.shape[-1], pred.shape[0], K, rois, roi_cls, B, sizes_dev, gt_boxes, gt_classes,
-         gt_count, G, float(iou_thresh), loss, ws)
+    if box_reg is None:
+        call("sfod_bpc_loss", pred, pred.shape[-1], pred.shape[0], K, rois, roi_cls, B, sizes_dev, gt_boxes, gt_classes,
+             gt_count, G, float(iou_thresh), loss, ws)
+    else:
+        call("sfod_bpc_loss_opt", pred, pred.shape[-1], pred.shape[0], K, rois, roi_cls, B, sizes_dev, gt_boxes,
+             gt_classes, gt_count, G, float(iou_thresh), loss, ws, *box_reg.weights, int(box_reg.cls_agnostic))
     return loss[0]
 
 
