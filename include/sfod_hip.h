@@ -466,21 +466,31 @@ int sfod_roi_build_samples(const float* boxes, const int32_t* cls, const int32_t
 int sfod_make_rois(const float* props, const int32_t* prop_count, int B, int P, float* rois,
                    void* stream);
 
-/* ---- K13: ROIAlign (tv roi_align aligned=True, adaptive sampling; Appendix A.11) on NHWC
- * features.  out: [R, PH*PW, C] (dt).  rois with batch index < 0 are padding rows: the forward writes zeros for them, the
- * backward ignores them.  pooled in [1, 16] (the backward: [1, 8]).
- * Definition (oracle/pointwise_definitions.py roi_align_matrices; held per element by tests/test_gpu_roi_definition.py, in
- * fp32, bf16 and on the exact values of operand pairs): out[r, ph, pw, c] = sum_{py, px} Ay[r, ph, py] Ax[r, pw, px]
- * feat[b_r, py, px, c] / count_r, Ay / Ax the bilinear weights of the bin's grid_h / grid_w sample rows / columns
- * (grid = ceil(roi_len / pooled), count = max(grid_h grid_w, 1); a zero-sized ROI has grid 0 and gives zeros), sample
- * coordinates in fp32 as torchvision writes them, a sample outside [-1, H] x [-1, W] dropped. */
+/* ---- K13: ROIAlign (tv roi_align; Appendix A.11) on NHWC features.  out: [R, PH*PW, C] (dt).  rois with batch index < 0 are
+ * padding rows: the forward writes zeros for them, the backward ignores them.  pooled in [1, 16], both directions.
+ * Definition (oracle/pointwise_definitions.py roi_align_matrices, with the options tests/helpers/roi_pooler_definitions.py;
+ * held per element by tests/test_gpu_roi_definition.py and tests/test_gpu_roi_pooler_options.py, in fp32, bf16 and on the
+ * exact values of operand pairs): out[r, ph, pw, c] = sum_{py, px} Ay[r, ph, py] Ax[r, pw, px] feat[b_r, py, px, c] / count_r,
+ * Ay / Ax the bilinear weights of the bin's grid_h / grid_w sample rows / columns, sample i of bin p at
+ * start + p * bin + (i + .5) * bin / grid with bin = roi_len / pooled, count = max(grid_h grid_w, 1), the coordinates in fp32
+ * as torchvision writes them, a sample outside [-1, H] x [-1, W] dropped.
+ *   aligned = 1 (d2 "ROIAlignV2"): start = coord * scale - 0.5, roi_len = end - start (a zero-sized ROI has grid 0 and gives zeros)
+ *   aligned = 0 (d2 "ROIAlign"):   start = coord * scale,       roi_len = max(end - start, 1)
+ *   sampling_ratio = 0: grid = ceil(roi_len / pooled) per ROI and axis;  sampling_ratio in [1, 16]: grid_h = grid_w = sampling_ratio
+ *     (a fixed grid samples an inverted ROI, end < start under aligned = 1, with its negative bin, like torchvision; both directions do)
+ * sfod_roi_align_fwd is sfod_roi_align_fwd_opt with (sampling_ratio, aligned) = (0, 1), likewise the backward. */
 int sfod_roi_align_fwd(const void* feat, int B, int H, int W, int C, const float* rois, int R,
                        int pooled, float scale, void* out, int dt, void* stream);
+int sfod_roi_align_fwd_opt(const void* feat, int B, int H, int W, int C, const float* rois, int R,
+                           int pooled, float scale, int sampling_ratio, int aligned, void* out, int dt, void* stream);
 /* dfeat fp32 [B,H,W,C] += adjoint of the forward above (zero-init by the caller, or an earlier gradient to add to).
- * pooled == 7: tiled gather, one owner per gradient element, ROIs summed in ROI order (bit-reproducible); other sizes: one
- * workgroup per ROI, separable interpolation weights, one float atomic per footprint pixel and channel */
+ * Tiled gather for every pooled size: one owner per gradient element, ROIs summed in ROI order, no float atomics
+ * (bit-reproducible).  SFOD_ROI_BWD_ATOMIC=1 (read at load; an A/B switch) selects, for pooled <= 8, one workgroup per ROI
+ * with one float atomic per footprint pixel and channel. */
 int sfod_roi_align_bwd(const void* dout, int B, int H, int W, int C, const float* rois, int R,
                        int pooled, float scale, float* dfeat, int dt, void* stream);
+int sfod_roi_align_bwd_opt(const void* dout, int B, int H, int W, int C, const float* rois, int R,
+                           int pooled, float scale, int sampling_ratio, int aligned, float* dfeat, int dt, void* stream);
 
 /* ---- K15: Fast R-CNN losses (Appendix A.12; roi_heads.py:124).  pred: fp32 [R, ld]: cols
  * [0,K] class scores, cols [K+1, K+1+4K) deltas.  loss[0]=loss_cls, loss[1]=loss_box_reg. */

@@ -210,8 +210,9 @@ def get_cfg():
     _C.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT = 1.0
     _C.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS = (10.0, 10.0, 5.0, 5.0)
     _C.MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA = 0.0
-    # d2's default.  The library's ROIAlign serves <= 16 forward and <= 8 backward: a TRAINING config has to set <= 8
-    # (the three named yamls set 7); StandardROIHeads raises at the first training forward otherwise.
+    # d2's defaults (the named yamls set 7).  Built: POOLER_RESOLUTION in [1, 16], POOLER_SAMPLING_RATIO in [0, 16],
+    # POOLER_TYPE "ROIAlignV2" / "ROIAlign" (modeling/roi_pooler.py).  StandardROIHeads.forward still refuses a TRAINING
+    # pass above 8 (pinned by tests/test_host_logic.py), though the kernels and the loss node train up to 16.
     _C.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION = 14
     _C.MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO = 0
     _C.MODEL.ROI_BOX_HEAD.POOLER_TYPE = "ROIAlignV2"

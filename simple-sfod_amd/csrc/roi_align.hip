@@ -1,15 +1,16 @@
-// ROIAlign (torchvision roi_align, aligned=True, adaptive sampling grid) on NHWC features.
+// ROIAlign (torchvision roi_align; aligned and sampling_ratio by value, defaults aligned=True, adaptive grid) on NHWC features.
 // Reference call site: daod/modeling/roi_heads/source_free_adaptive_teacher_roi_heads.py:117
 // (box_pooler = d2 ROIPooler -> ROIAlign(7, 1/stride, 0, aligned=True)); SURVEY A.11.
 //
 // Forward: one workgroup per ROI, 16-byte channel vectors across the lanes; the feature map of the
 // hot config is 37x75x512 (2.8 MB in bf16) and stays L2-resident, so the [R,49,C] output writes are the
-// HBM traffic.  Backward: tiled gather (one owner per gradient element, no atomics) for pooled == 7.
+// HBM traffic.  Backward: tiled gather (one owner per gradient element, no atomics) for every pooled size in [1, 16].
 #include "conv_internal.h"
 #include <cstdlib>
 
-#define ROI_MAXP 8
-#define ROI_MAXP_FWD 16
+#define ROI_MAXP 8            // register tile of the atomic backward (SFOD_ROI_BWD_ATOMIC=1)
+#define ROI_MAXP_FWD 16       // largest pooled size, both directions
+#define ROI_MAX_SAMPLING 16
 #define ROI_CBLK_DEFAULT 128
 #define ROI_NT_DEFAULT 1
 
@@ -40,18 +41,21 @@ struct RoiGeom {
   float count;
 };
 
-__device__ __forceinline__ RoiGeom roi_geom(const float* roi, float scale, int pooled) {
+// aligned = 1: half-pixel offset, the ROI's raw length (a zero-sized ROI has grid 0 and gives zeros); aligned = 0: no offset,
+// the length clamped to >= 1 (torchvision's legacy form).  sampling_ratio > 0 fixes the grid of every ROI; 0: ceil(bin).
+__device__ __forceinline__ RoiGeom roi_geom(const float* roi, float scale, int pooled, int sampling_ratio, int aligned) {
   RoiGeom g;
   g.b = (int)roi[0];
-  const float offset = 0.5f;  // aligned=True
+  const float offset = aligned ? 0.5f : 0.f;
   g.start_w = roi[1] * scale - offset;
   g.start_h = roi[2] * scale - offset;
   const float end_w = roi[3] * scale - offset, end_h = roi[4] * scale - offset;
-  const float roi_w = end_w - g.start_w, roi_h = end_h - g.start_h;
+  float roi_w = end_w - g.start_w, roi_h = end_h - g.start_h;
+  if (!aligned) { roi_w = fmaxf(roi_w, 1.f); roi_h = fmaxf(roi_h, 1.f); }
   g.bin_h = roi_h / (float)pooled;
   g.bin_w = roi_w / (float)pooled;
-  g.grid_h = (int)ceilf(roi_h / (float)pooled);
-  g.grid_w = (int)ceilf(roi_w / (float)pooled);
+  g.grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_h / (float)pooled);
+  g.grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_w / (float)pooled);
   const int c = g.grid_h * g.grid_w;
   g.count = (float)(c > 1 ? c : 1);
   return g;
@@ -118,7 +122,7 @@ template <> struct RVec<splith_t> {     // SFOD_F16X3: the same with half pairs
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_roi_align_fwd(const T* __restrict__ feat, int H, int W, int C, const float* __restrict__ rois,
-                int pooled, float scale, T* __restrict__ out) {
+                int pooled, float scale, int sampling_ratio, int aligned, T* __restrict__ out) {
   constexpr int V = RVec<T>::N;
   const int r = blockIdx.x;
   const float* roi = rois + (int64_t)r * 5;
@@ -137,7 +141,7 @@ k_roi_align_fwd(const T* __restrict__ feat, int H, int W, int C, const float* __
       for (int c = cl; c < cv; c += clanes) RVec<T>::store(orow + (int64_t)bin * C + c * V, z);
     return;
   }
-  const RoiGeom g = roi_geom(roi, scale, pooled);
+  const RoiGeom g = roi_geom(roi, scale, pooled, sampling_ratio, aligned);
   const T* fb = feat + (int64_t)g.b * H * W * C;
   for (int bin = bl; bin < nbins; bin += blanes) {
     const int ph = bin / pooled, pw = bin % pooled;
@@ -201,7 +205,7 @@ template <> struct Pair<splith_t> {
 template <typename T, int P, bool NT>
 __global__ void __launch_bounds__(256)
 k_roi_align_fwd_sep(const T* __restrict__ feat, int H, int W, int C, const float* __restrict__ rois, float scale,
-                    T* __restrict__ out, int R, int ncb) {
+                    int sampling_ratio, int aligned, T* __restrict__ out, int R, int ncb) {
   extern __shared__ __attribute__((aligned(16))) float sw[];   // Ay [P][H], Ax [P][W], then int sup[2 * P][2]
   // grid = ncb channel blocks x R boxes, channel-block major: at any time the chip works on ONE slice of C / ncb channels of
   // the feature map, which has to stay in an XCD's 4 MB L2 across the boxes that share it -- with all 1024 channels per
@@ -222,7 +226,7 @@ k_roi_align_fwd_sep(const T* __restrict__ feat, int H, int W, int C, const float
     }
     return;
   }
-  const RoiGeom g = roi_geom(roi, scale, P);
+  const RoiGeom g = roi_geom(roi, scale, P, sampling_ratio, aligned);
   float* Ay = sw;
   float* Ax = sw + P * H;
   int* sup = reinterpret_cast<int*>(Ax + P * W);            // [ph] (ylo, yhi), then [pw] (xlo, xhi): support of each row
@@ -320,13 +324,13 @@ k_roi_align_fwd_sep(const T* __restrict__ feat, int H, int W, int C, const float
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_roi_align_bwd(const T* __restrict__ dout, int H, int W, int C, const float* __restrict__ rois,
-                int pooled, float scale, float* __restrict__ dfeat) {
+                int pooled, float scale, int sampling_ratio, int aligned, float* __restrict__ dfeat) {
   extern __shared__ __attribute__((aligned(16))) float sw[];   // Ay [pooled][H], Ax [pooled][W], then int lim[4]
   const int r = blockIdx.x;
   const float* roi = rois + (int64_t)r * 5;
   if (roi[0] < 0.f) return;
   const int nbins = pooled * pooled;
-  const RoiGeom g = roi_geom(roi, scale, pooled);
+  const RoiGeom g = roi_geom(roi, scale, pooled, sampling_ratio, aligned);
   float* Ay = sw;
   float* Ax = sw + pooled * H;
   int* lim = reinterpret_cast<int*>(Ax + pooled * W);            // ylo, yhi, xlo, xhi
@@ -394,24 +398,28 @@ k_roi_align_bwd(const T* __restrict__ dout, int H, int W, int C, const float* __
   }
 }
 
-// Backward, gather form (pooled == 7).  One workgroup owns an 8x8-pixel tile of one image's gradient map
+// Backward, gather form (every pooled size).  One workgroup owns an 8x8-pixel tile of one image's gradient map
 // for a 256-channel slice: it lists the ROIs whose footprint touches the tile (in ROI order: ballot +
 // prefix, so the fp32 summation order is fixed), then for each of them forms the tile-restricted
-// separable weights Ay [7][8] / Ax [7][8] (14 threads, double-buffered in LDS) and every thread (one
-// channel) accumulates  acc[py][px] += sum_ph Ay[ph][py] * (sum_pw Ax[pw][px] * g[ph][pw])  in
+// separable weights Ay [P][8] / Ax [P][8] (2P threads, double-buffered in LDS) and every thread (one
+// channel) accumulates  acc[py][px] += sum_ph Ay[ph][py] * (sum_pw Ax[pw][px] / count * g[ph][pw])  in
 // registers.  Each gradient element has exactly one owner: no atomics, one read-modify-write of the
-// tile at the end, and the result is bit-reproducible.  Bin rows / columns whose weights are all zero
-// inside the tile are skipped (wave-uniform masks).
+// tile at the end, and the result is bit-reproducible.  Bin rows whose weights are all zero inside the
+// tile are skipped (wave-uniform masks).
+// PC > 0: the pooled size at compile time, the P x P upstream values of the ROI in registers (PC = 7, the configs' size).
+// PC == 0: the pooled size at run time, up to ROI_MAXP_FWD: one bin row of upstream values in registers at a time, Ax / count
+// read from LDS (P x P registers would spill beyond 8); the same fmaf order over pw, then ph.
 constexpr int RT = 8;            // tile edge in feature pixels
 constexpr int RT_LIST = 4096;    // ROI ids listed per pass
 
-template <typename T>
+template <typename T, int PC>
 __global__ void __launch_bounds__(256)
 k_roi_align_bwd_tiled(const T* __restrict__ dout, int H, int W, int C, const float* __restrict__ rois, int R,
-                      float scale, float* __restrict__ dfeat) {
-  constexpr int P = 7;
+                      int pooled, float scale, int sampling_ratio, int aligned, float* __restrict__ dfeat) {
+  constexpr int PW = PC > 0 ? PC : ROI_MAXP_FWD;       // rows of the weight buffers
+  const int P = PC > 0 ? PC : pooled;
   __shared__ int list[RT_LIST];
-  __shared__ __attribute__((aligned(16))) float wts[2][2][P][RT];   // [buffer][y|x][bin][pixel]
+  __shared__ __attribute__((aligned(16))) float wts[2][2][PW][RT];   // [buffer][y|x][bin][pixel]
   __shared__ int masks[2][2];
   __shared__ int wtot[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -428,7 +436,7 @@ k_roi_align_bwd_tiled(const T* __restrict__ dout, int H, int W, int C, const flo
 
   // weights of ROI r restricted to the tile -> buffer `buf`; run by threads 0 .. 2P-1
   auto build = [&](int r, int buf) {
-    const RoiGeom g = roi_geom(rois + (int64_t)r * 5, scale, P);
+    const RoiGeom g = roi_geom(rois + (int64_t)r * 5, scale, P, sampling_ratio, aligned);
     const bool isy = tid < P;
     const int p = isy ? tid : tid - P;
     const int L = isy ? H : W, o = isy ? y0 : x0;
@@ -450,10 +458,12 @@ k_roi_align_bwd_tiled(const T* __restrict__ dout, int H, int W, int C, const flo
         if (hgh - o == k) row[k] += lw;
       }
     }
+    // PC == 0: the x weights are stored divided by count (what the PC > 0 form does in registers, the same product)
+    const float sc = (PC == 0 && !isy) ? 1.f / g.count : 1.f;
     bool nz = false;
 #pragma unroll
     for (int k = 0; k < RT; ++k) {
-      wts[buf][isy ? 0 : 1][p][k] = row[k];
+      wts[buf][isy ? 0 : 1][p][k] = PC == 0 ? row[k] * sc : row[k];
       nz |= row[k] != 0.f;
     }
     if (nz) atomicOr(&masks[buf][isy ? 0 : 1], 1 << p);
@@ -469,13 +479,19 @@ k_roi_align_bwd_tiled(const T* __restrict__ dout, int H, int W, int C, const flo
       if (r < rend) {
         const float* roi = rois + (int64_t)r * 5;
         if (roi[0] >= 0.f && (int)roi[0] == b) {
-          const RoiGeom g = roi_geom(roi, scale, P);
+          const RoiGeom g = roi_geom(roi, scale, P, sampling_ratio, aligned);
           if (g.grid_h > 0 && g.grid_w > 0) {
-            // footprint bound: samples lie in [start, start + P*bin], a sample touches floor(v), floor(v)+1
+            // footprint bound: samples lie between start and start + P*bin, a sample touches floor(v), floor(v)+1.  bin is
+            // (clamped length) / P under either alignment and a sample sits at start + (p + (i + .5) / grid) * bin with
+            // p <= P - 1 and (i + .5) / grid < 1 for the adaptive and the fixed grid alike.  Under a fixed grid an inverted ROI
+            // (end < start, aligned) keeps its samples with a NEGATIVE bin: the interval is taken by min / max of its ends
+            // (for bin >= 0 the same values as before).  tests/test_roi_pooler_options_host.py restates it on fp32 coordinates.
             const float eh = g.start_h + (float)P * g.bin_h, ew = g.start_w + (float)P * g.bin_w;
-            const int ylo = (int)fmaxf(g.start_h, 0.f), yhi = min((int)fmaxf(eh, 0.f) + 1, H - 1);
-            const int xlo = (int)fmaxf(g.start_w, 0.f), xhi = min((int)fmaxf(ew, 0.f) + 1, W - 1);
-            hit = eh >= -1.f && ew >= -1.f && g.start_h <= (float)H && g.start_w <= (float)W &&
+            const float lh = fminf(g.start_h, eh), hh = fmaxf(g.start_h, eh);
+            const float lw = fminf(g.start_w, ew), hw = fmaxf(g.start_w, ew);
+            const int ylo = (int)fmaxf(lh, 0.f), yhi = min((int)fmaxf(hh, 0.f) + 1, H - 1);
+            const int xlo = (int)fmaxf(lw, 0.f), xhi = min((int)fmaxf(hw, 0.f) + 1, W - 1);
+            hit = hh >= -1.f && hw >= -1.f && lh <= (float)H && lw <= (float)W &&
                   ylo < y0 + RT && yhi >= y0 && xlo < x0 + RT && xhi >= x0;
           }
         }
@@ -502,42 +518,76 @@ k_roi_align_bwd_tiled(const T* __restrict__ dout, int H, int W, int C, const flo
       if (i + 1 < n && tid < 2 * P) build(list[i + 1], buf ^ 1);
       if (ym != 0 && xm != 0 && cok) {
         const int r = list[i];
-        const float* roi = rois + (int64_t)r * 5;
-        const RoiGeom g = roi_geom(roi, scale, P);
-        const float inv = 1.f / g.count;
-        const T* grow = dout + (int64_t)r * (P * P) * C + c;
-        float gv[P][P];
+        if constexpr (PC > 0) {
+          const float* roi = rois + (int64_t)r * 5;
+          const RoiGeom g = roi_geom(roi, scale, P, sampling_ratio, aligned);
+          const float inv = 1.f / g.count;
+          const T* grow = dout + (int64_t)r * (PC * PC) * C + c;
+          float gv[PC][PC];
 #pragma unroll
-        for (int ph = 0; ph < P; ++ph)
+          for (int ph = 0; ph < PC; ++ph)
 #pragma unroll
-          for (int pw = 0; pw < P; ++pw)
-            gv[ph][pw] = to_f32(grow[(int64_t)(ph * P + pw) * C]);   // unconditional: all 49 in flight
-        float ax[P][RT];
+            for (int pw = 0; pw < PC; ++pw)
+              gv[ph][pw] = to_f32(grow[(int64_t)(ph * PC + pw) * C]);   // unconditional: all P x P in flight
+          float ax[PC][RT];
 #pragma unroll
-        for (int pw = 0; pw < P; ++pw) {
-          const float4 a0 = *reinterpret_cast<const float4*>(&wts[buf][1][pw][0]);
-          const float4 a1 = *reinterpret_cast<const float4*>(&wts[buf][1][pw][4]);
-          ax[pw][0] = a0.x * inv; ax[pw][1] = a0.y * inv; ax[pw][2] = a0.z * inv; ax[pw][3] = a0.w * inv;
-          ax[pw][4] = a1.x * inv; ax[pw][5] = a1.y * inv; ax[pw][6] = a1.z * inv; ax[pw][7] = a1.w * inv;
-        }
-#pragma unroll
-        for (int ph = 0; ph < P; ++ph) {
-          if (!((ym >> ph) & 1)) continue;
-          float t[RT];
-#pragma unroll
-          for (int px = 0; px < RT; ++px) {
-            float a = 0.f;
-#pragma unroll
-            for (int pw = 0; pw < P; ++pw) a = fmaf(ax[pw][px], gv[ph][pw], a);
-            t[px] = a;
+          for (int pw = 0; pw < PC; ++pw) {
+            const float4 a0 = *reinterpret_cast<const float4*>(&wts[buf][1][pw][0]);
+            const float4 a1 = *reinterpret_cast<const float4*>(&wts[buf][1][pw][4]);
+            ax[pw][0] = a0.x * inv; ax[pw][1] = a0.y * inv; ax[pw][2] = a0.z * inv; ax[pw][3] = a0.w * inv;
+            ax[pw][4] = a1.x * inv; ax[pw][5] = a1.y * inv; ax[pw][6] = a1.z * inv; ax[pw][7] = a1.w * inv;
           }
-          const float4 b0 = *reinterpret_cast<const float4*>(&wts[buf][0][ph][0]);
-          const float4 b1 = *reinterpret_cast<const float4*>(&wts[buf][0][ph][4]);
-          const float ay[RT] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
-          for (int py = 0; py < RT; ++py)
+          for (int ph = 0; ph < PC; ++ph) {
+            if (!((ym >> ph) & 1)) continue;
+            float t[RT];
 #pragma unroll
-            for (int px = 0; px < RT; ++px) acc[py][px] = fmaf(ay[py], t[px], acc[py][px]);
+            for (int px = 0; px < RT; ++px) {
+              float a = 0.f;
+#pragma unroll
+              for (int pw = 0; pw < PC; ++pw) a = fmaf(ax[pw][px], gv[ph][pw], a);
+              t[px] = a;
+            }
+            const float4 b0 = *reinterpret_cast<const float4*>(&wts[buf][0][ph][0]);
+            const float4 b1 = *reinterpret_cast<const float4*>(&wts[buf][0][ph][4]);
+            const float ay[RT] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+            for (int py = 0; py < RT; ++py)
+#pragma unroll
+              for (int px = 0; px < RT; ++px) acc[py][px] = fmaf(ay[py], t[px], acc[py][px]);
+          }
+        } else {
+          const T* grow = dout + (int64_t)r * (P * P) * C;       // wave-uniform; the lane adds its channel
+          for (int ph = 0; ph < P; ++ph) {
+            if (!((ym >> ph) & 1)) continue;
+            // one bin row of upstream values; a column index beyond P re-reads the row's last element (inside the ROI's
+            // P x P block: no out-of-bounds address, no branch around the load) and is left out of the sum below
+            float gr[PW];
+#pragma unroll
+            for (int pw = 0; pw < PW; ++pw)
+              gr[pw] = to_f32((grow + (int64_t)(ph * P + min(pw, P - 1)) * C)[c]);
+            float t[RT];
+#pragma unroll
+            for (int px = 0; px < RT; ++px) t[px] = 0.f;
+#pragma unroll
+            for (int pw = 0; pw < PW; ++pw) {
+              if (pw < P) {                                   // wave-uniform
+                const float4 a0 = *reinterpret_cast<const float4*>(&wts[buf][1][pw][0]);
+                const float4 a1 = *reinterpret_cast<const float4*>(&wts[buf][1][pw][4]);
+                t[0] = fmaf(a0.x, gr[pw], t[0]); t[1] = fmaf(a0.y, gr[pw], t[1]);
+                t[2] = fmaf(a0.z, gr[pw], t[2]); t[3] = fmaf(a0.w, gr[pw], t[3]);
+                t[4] = fmaf(a1.x, gr[pw], t[4]); t[5] = fmaf(a1.y, gr[pw], t[5]);
+                t[6] = fmaf(a1.z, gr[pw], t[6]); t[7] = fmaf(a1.w, gr[pw], t[7]);
+              }
+            }
+            const float4 b0 = *reinterpret_cast<const float4*>(&wts[buf][0][ph][0]);
+            const float4 b1 = *reinterpret_cast<const float4*>(&wts[buf][0][ph][4]);
+            const float ay[RT] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+            for (int py = 0; py < RT; ++py)
+#pragma unroll
+              for (int px = 0; px < RT; ++px) acc[py][px] = fmaf(ay[py], t[px], acc[py][px]);
+          }
         }
       }
       __syncthreads();
@@ -556,34 +606,41 @@ k_roi_align_bwd_tiled(const T* __restrict__ dout, int H, int W, int C, const flo
     }
 }
 
-// SFOD_ROI_BWD_ATOMIC=1 selects the scatter (atomic) form for A/B measurements.
+// SFOD_ROI_BWD_ATOMIC=1 selects the scatter (atomic) form for A/B measurements (pooled <= 8: its register tile).
 static const bool g_roi_bwd_tiled = []() { const char* e = getenv("SFOD_ROI_BWD_ATOMIC"); return !(e && e[0] == '1'); }();
 
 template <typename T>
 static int dispatch_roi_bwd(const void* dout, int B, int H, int W, int C, const float* rois, int R, int pooled,
-                            float scale, float* dfeat, hipStream_t s) {
-  if (pooled == 7 && g_roi_bwd_tiled) {
+                            float scale, int sampling_ratio, int aligned, float* dfeat, hipStream_t s) {
+  if (g_roi_bwd_tiled || pooled > ROI_MAXP) {
     const dim3 grid(((H + RT - 1) / RT) * ((W + RT - 1) / RT), (C + 255) / 256, B);
-    hipLaunchKernelGGL(k_roi_align_bwd_tiled<T>, grid, dim3(256), 0, s, (const T*)dout, H, W, C, rois, R, scale,
-                       dfeat);
+    if (pooled == 7)
+      hipLaunchKernelGGL((k_roi_align_bwd_tiled<T, 7>), grid, dim3(256), 0, s, (const T*)dout, H, W, C, rois, R, pooled,
+                         scale, sampling_ratio, aligned, dfeat);
+    else
+      hipLaunchKernelGGL((k_roi_align_bwd_tiled<T, 0>), grid, dim3(256), 0, s, (const T*)dout, H, W, C, rois, R, pooled,
+                         scale, sampling_ratio, aligned, dfeat);
     return sfod_check_launch("roi_align_bwd_tiled");
   }
   const size_t lds = (size_t)pooled * (H + W) * 4 + 16;
   SFOD_REQUIRE(lds <= 64 * 1024, "roi_align_bwd: feature map too large");
   hipLaunchKernelGGL(k_roi_align_bwd<T>, dim3(R), dim3(256), lds, s, (const T*)dout, H, W, C, rois, pooled, scale,
-                     dfeat);
+                     sampling_ratio, aligned, dfeat);
   return sfod_check_launch("roi_align_bwd");
 }
 
-extern "C" int sfod_roi_align_fwd(const void* feat, int B, int H, int W, int C, const float* rois, int R,
-                                  int pooled, float scale, void* out, int dt, void* stream) {
+extern "C" int sfod_roi_align_fwd_opt(const void* feat, int B, int H, int W, int C, const float* rois, int R,
+                                      int pooled, float scale, int sampling_ratio, int aligned, void* out, int dt,
+                                      void* stream) {
   SFOD_REQUIRE_EXTENTS("roi_align_fwd", B, H, W, C, R, pooled);
   (void)B;
   if (R == 0) return 0;
   SFOD_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1, "roi_align: empty feature map");
-  // (the backward's register tiles bound it at 8; the forward's bin loop has no such limit: 14 is Detectron2's default
-  // POOLER_RESOLUTION, the size its own unit tests' golden losses are computed at -- tests/test_gpu_d2_golden.py)
+  // 14 is Detectron2's default POOLER_RESOLUTION, the size its own unit tests' golden losses are computed at
+  // (tests/test_gpu_d2_golden.py)
   SFOD_REQUIRE(pooled >= 1 && pooled <= ROI_MAXP_FWD, "roi_align: pooled size must be in [1, 16]");
+  SFOD_REQUIRE(sampling_ratio >= 0 && sampling_ratio <= ROI_MAX_SAMPLING, "roi_align: sampling_ratio must be in [0, 16]");
+  SFOD_REQUIRE(aligned == 0 || aligned == 1, "roi_align: aligned must be 0 or 1");
   SFOD_REQUIRE(dt == SFOD_F32 || dt == SFOD_BF16 || sfod_is_pairs(dt), "roi_align: unknown dt");
   SFOD_REQUIRE(feat != nullptr && rois != nullptr && out != nullptr, "roi_align: null argument (feat, rois, out)");
   SFOD_REQUIRE(sfod_prod_fits({B, H, W, C}, 1LL << 40) && sfod_prod_fits({R, C, pooled, pooled}, 1LL << 40) &&
@@ -591,7 +648,9 @@ extern "C" int sfod_roi_align_fwd(const void* feat, int B, int H, int W, int C, 
   SFOD_REQUIRE(C % ((dt == SFOD_F32) ? 4 : 8) == 0, "roi_align: C must be a multiple of the 16-byte vector");
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)pooled * (H + W) * 4 + 4 * pooled * 4;
-  if (pooled == 7 && lds <= 48 * 1024) {       // the configs' POOLER_RESOLUTION: separable form
+  // SFOD_ROI_FWD_SEP14=0: the sample-by-sample kernel at 14 (A/B)
+  static const bool sep14 = []() { const char* e = getenv("SFOD_ROI_FWD_SEP14"); return !(e && e[0] == '0'); }();
+  if ((pooled == 7 || (pooled == 14 && sep14)) && lds <= 48 * 1024) {       // the configs' POOLER_RESOLUTION and d2's default: separable form
     // channel blocks (one L2-resident slice of the feature map at a time); SFOD_ROI_CBLK: logical channels per block
     // (A/B; 0: one workgroup per box), SFOD_ROI_NT=1: non-temporal output stores
     static const int cblk_env = []() { const char* e = getenv("SFOD_ROI_CBLK"); return e ? atoi(e) : ROI_CBLK_DEFAULT; }();
@@ -600,47 +659,64 @@ extern "C" int sfod_roi_align_fwd(const void* feat, int B, int H, int W, int C, 
     int ncb = 1;
     if (cblk_env > 0 && cblk_env % V == 0 && C % cblk_env == 0 && C > cblk_env) ncb = C / cblk_env;
     const int cblk = C / ncb;
-    // threads: one lane per 16-byte (pairs: 32-byte) channel vector of the block x 8 bin-row groups (7 active)
-    int threads = (cblk / V) * 8;
+    // threads: one lane per 16-byte (pairs: 32-byte) channel vector of the block x 8 bin-row groups (7 active; 14: 16 groups)
+    int threads = (cblk / V) * (pooled == 7 ? 8 : 16);
     threads = threads < 64 ? 64 : (threads > 256 ? 256 : threads);
     const dim3 grid((unsigned)R * ncb), block((unsigned)threads);
-#define SFOD_ROI_SEP(T_, NT_) hipLaunchKernelGGL((k_roi_align_fwd_sep<T_, 7, NT_>), grid, block, lds, s, (const T_*)feat, H, W, C, \
-                                                 rois, scale, (T_*)out, R, ncb)
-    if (dt == SFOD_F32) { if (nt) SFOD_ROI_SEP(float, true); else SFOD_ROI_SEP(float, false); }
-    else if (dt == SFOD_BF16X3) { if (nt) SFOD_ROI_SEP(split_t, true); else SFOD_ROI_SEP(split_t, false); }
-    else if (dt == SFOD_F16X3) { if (nt) SFOD_ROI_SEP(splith_t, true); else SFOD_ROI_SEP(splith_t, false); }
-    else { if (nt) SFOD_ROI_SEP(bf16_t, true); else SFOD_ROI_SEP(bf16_t, false); }
+#define SFOD_ROI_SEP(T_, P_, NT_) hipLaunchKernelGGL((k_roi_align_fwd_sep<T_, P_, NT_>), grid, block, lds, s, (const T_*)feat, H, W, C, \
+                                                     rois, scale, sampling_ratio, aligned, (T_*)out, R, ncb)
+#define SFOD_ROI_SEP_P(T_) do { if (pooled == 7) { if (nt) SFOD_ROI_SEP(T_, 7, true); else SFOD_ROI_SEP(T_, 7, false); } \
+                                else { if (nt) SFOD_ROI_SEP(T_, 14, true); else SFOD_ROI_SEP(T_, 14, false); } } while (0)
+    if (dt == SFOD_F32) SFOD_ROI_SEP_P(float);
+    else if (dt == SFOD_BF16X3) SFOD_ROI_SEP_P(split_t);
+    else if (dt == SFOD_F16X3) SFOD_ROI_SEP_P(splith_t);
+    else SFOD_ROI_SEP_P(bf16_t);
+#undef SFOD_ROI_SEP_P
 #undef SFOD_ROI_SEP
     return sfod_check_launch("roi_align_fwd_sep");
   }
   if (dt == SFOD_F32)
     hipLaunchKernelGGL(k_roi_align_fwd<float>, dim3(R), dim3(256), 0, s, (const float*)feat, H, W, C, rois,
-                       pooled, scale, (float*)out);
+                       pooled, scale, sampling_ratio, aligned, (float*)out);
   else if (dt == SFOD_BF16X3)
     hipLaunchKernelGGL(k_roi_align_fwd<split_t>, dim3(R), dim3(256), 0, s, (const split_t*)feat, H, W, C, rois,
-                       pooled, scale, (split_t*)out);
+                       pooled, scale, sampling_ratio, aligned, (split_t*)out);
   else if (dt == SFOD_F16X3)
     hipLaunchKernelGGL(k_roi_align_fwd<splith_t>, dim3(R), dim3(256), 0, s, (const splith_t*)feat, H, W, C, rois,
-                       pooled, scale, (splith_t*)out);
+                       pooled, scale, sampling_ratio, aligned, (splith_t*)out);
   else
     hipLaunchKernelGGL(k_roi_align_fwd<bf16_t>, dim3(R), dim3(256), 0, s, (const bf16_t*)feat, H, W, C,
-                       rois, pooled, scale, (bf16_t*)out);
+                       rois, pooled, scale, sampling_ratio, aligned, (bf16_t*)out);
   return sfod_check_launch("roi_align_fwd");
 }
 
-extern "C" int sfod_roi_align_bwd(const void* dout, int B, int H, int W, int C, const float* rois, int R,
-                                  int pooled, float scale, float* dfeat, int dt, void* stream) {
+extern "C" int sfod_roi_align_fwd(const void* feat, int B, int H, int W, int C, const float* rois, int R,
+                                  int pooled, float scale, void* out, int dt, void* stream) {
+  return sfod_roi_align_fwd_opt(feat, B, H, W, C, rois, R, pooled, scale, 0, 1, out, dt, stream);
+}
+
+extern "C" int sfod_roi_align_bwd_opt(const void* dout, int B, int H, int W, int C, const float* rois, int R,
+                                      int pooled, float scale, int sampling_ratio, int aligned, float* dfeat, int dt,
+                                      void* stream) {
   SFOD_REQUIRE_EXTENTS("roi_align_bwd", B, H, W, C, R, pooled);
   if (R == 0 || B == 0) return 0;
   SFOD_REQUIRE(C % 8 == 0, "roi_align_bwd: C must be a multiple of 8");
-  SFOD_REQUIRE(pooled >= 1 && pooled <= ROI_MAXP, "roi_align_bwd: pooled size must be <= 8");
+  SFOD_REQUIRE(pooled >= 1 && pooled <= ROI_MAXP_FWD, "roi_align_bwd: pooled size must be in [1, 16]");
+  SFOD_REQUIRE(sampling_ratio >= 0 && sampling_ratio <= ROI_MAX_SAMPLING, "roi_align_bwd: sampling_ratio must be in [0, 16]");
+  SFOD_REQUIRE(aligned == 0 || aligned == 1, "roi_align_bwd: aligned must be 0 or 1");
   SFOD_REQUIRE(dout != nullptr && rois != nullptr && dfeat != nullptr, "roi_align_bwd: null argument (dout, rois, dfeat)");
   SFOD_REQUIRE(sfod_prod_fits({B, H, W, C}, 1LL << 40) && sfod_prod_fits({R, C, pooled, pooled}, 1LL << 40),
                "roi_align_bwd: oversized problem");
   hipStream_t s = (hipStream_t)stream;
   SFOD_REQUIRE(!sfod_is_pairs(dt), "roi_align_bwd: the upstream gradient is fp32 in the operand-pair modes");
-  if (dt == SFOD_F32) return dispatch_roi_bwd<float>(dout, B, H, W, C, rois, R, pooled, scale, dfeat, s);
-  return dispatch_roi_bwd<bf16_t>(dout, B, H, W, C, rois, R, pooled, scale, dfeat, s);
+  if (dt == SFOD_F32)
+    return dispatch_roi_bwd<float>(dout, B, H, W, C, rois, R, pooled, scale, sampling_ratio, aligned, dfeat, s);
+  return dispatch_roi_bwd<bf16_t>(dout, B, H, W, C, rois, R, pooled, scale, sampling_ratio, aligned, dfeat, s);
+}
+
+extern "C" int sfod_roi_align_bwd(const void* dout, int B, int H, int W, int C, const float* rois, int R,
+                                  int pooled, float scale, float* dfeat, int dt, void* stream) {
+  return sfod_roi_align_bwd_opt(dout, B, H, W, C, rois, R, pooled, scale, 0, 1, dfeat, dt, stream);
 }
 
 SFOD_DEFINE_F16_POLL(sfod_f16_poll_roi)

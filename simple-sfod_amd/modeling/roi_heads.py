@@ -5,7 +5,8 @@ Mirrors ``/root/reference/daod/modeling/roi_heads/source_free_adaptive_teacher_r
 ``_init_box_head`` ``:27-66``, ``forward`` ``:68-106`` (training+compute_loss -> label & sample,
 4-tuple; otherwise inference, 2-tuple), ``_forward_box`` ``:108-163``,
 ``label_and_sample_proposals`` ``:165-215``; and the Detectron2 pieces it inherits (SURVEY.md
-A.11-A.13): add_ground_truth_to_proposals, Matcher [0.5], subsample 512 @ 0.25, ROIAlignV2 7x7,
+A.11-A.13): add_ground_truth_to_proposals, Matcher [0.5], subsample 512 @ 0.25, ROIAlignV2 7x7 (POOLER_TYPE,
+POOLER_SAMPLING_RATIO and POOLER_RESOLUTION <= 16 are built: modeling/roi_pooler.py),
 FastRCNNConvFCHead (2 FC), FastRCNNOutputLayers losses / inference.
 
 State-dict keys: ``roi_heads.box_head.fc{1,2}.*``, ``roi_heads.box_predictor.{cls_score,bbox_pred}.*``.
@@ -21,15 +22,22 @@ from ..structures import Boxes, Instances, ShapeSpec
 from .offchain import OffChain as _OffChain
 from .batched import BatchedDetections, BatchedGT, BatchedProposals
 from .box_regression import ROI_DEFAULT_WEIGHTS, roi_box_reg_options
+from .roi_pooler import roi_pooler_options
 
 
 class ROIPooler(nn.Module):
-    """Single-level ROIAlignV2 pooler (aligned=True).  Attributes read from outside
-    (source_free_adaptive_teacher_rcnn.py:190-194) are kept."""
+    """Single-level ROIAlign pooler: ``pooler_type`` "ROIAlignV2" (aligned=True) or "ROIAlign" (aligned=False), an integer
+    ``sampling_ratio`` in [0, 16] (0: the adaptive grid), ``output_size`` in [1, 16]; anything else raises a ValueError
+    naming the key (modeling/roi_pooler.py).  Attributes read from outside (source_free_adaptive_teacher_rcnn.py:190-194)
+    are kept.  ``options`` is what the native calls take: empty = the default entry points."""
 
-    def __init__(self, output_size, scales, sampling_ratio, pooler_type):
+    def __init__(self, output_size, scales, sampling_ratio, pooler_type, prefix="MODEL.ROI_BOX_HEAD"):
         super().__init__()
-        assert pooler_type == "ROIAlignV2" and sampling_ratio == 0 and len(scales) == 1
+        assert len(scales) == 1
+        output_size, self.sampling_ratio, self.aligned = roi_pooler_options(output_size, sampling_ratio, pooler_type, prefix)
+        self.pooler_type = pooler_type
+        self.options = {} if (self.sampling_ratio == 0 and self.aligned) else \
+            {"sampling_ratio": self.sampling_ratio, "aligned": self.aligned}
         self.output_size = (output_size, output_size)
         self.scale = scales[0]
         min_level = -(math.log2(scales[0]))
@@ -313,7 +321,7 @@ class StandardROIHeads(nn.Module):
         bh, bp = self.box_head, self.box_predictor
         C, PP = self.channels, self.pooled * self.pooled
         pk = self.__dict__.pop("_packed", None) or {}
-        pooled = native.roi_align_fwd(feat, rois, self.pooled, self.box_pooler.scale)
+        pooled = native.roi_align_fwd(feat, rois, self.pooled, self.box_pooler.scale, **self.box_pooler.options)
         R = pooled.shape[0]
         x0 = pooled.view(R, PP * C)
         w1 = pk["w1"] if pk else native.pack_fc_weight(bh.fc1.weight.detach(), dt, chw_c=C)
@@ -390,7 +398,7 @@ class StandardROIHeads(nn.Module):
         dx0 = native.conv_fwd(dh1, w1t, None, bh.fc1.in_features, 1)
         B, H, W, _ = st["feat_shape"]
         dfeat = native.roi_align_bwd(dx0.view(-1, self.pooled * self.pooled, C), rois, (B, H, W, C), self.pooled,
-                                     self.box_pooler.scale)
+                                     self.box_pooler.scale, **self.box_pooler.options)
         off.join(dw1, db1, dw2, db2)     # the heads' gradients are final before anyone (all-reduce, SGD, autograd) reads them
         return dfeat.permute(0, 3, 1, 2), [dw1, db1, dw2, db2]
 
@@ -438,11 +446,13 @@ class StandardROIHeads(nn.Module):
         if (self.training and compute_loss) or compute_val_loss:
             assert targets is not None
             if self.pooled > 8 and torch.is_grad_enabled():
-                # sfod_roi_align_bwd's register tiles stop at 8 (the forward serves <= 16: Detectron2's unit-test size); say so
-                # BEFORE the losses, not in the first backward.  config.py's default is d2's 14: the named yamls set 7.
+                # The ROIAlign kernels serve <= 16 in both directions (the gather backward: csrc/roi_align.hip), and
+                # ``_box_forward`` / ``_box_head_backward`` / ``_ROILossFn`` train at any of them.  This module-level refusal
+                # of a TRAINING forward above 8 is kept as it was: tests/test_host_logic.py pins it.  config.py's default is
+                # d2's 14: the named yamls set 7.
                 # (Checked here, not in _box_forward: inside an autograd.Function's forward grad mode is always off.)
-                raise ValueError(f"MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION {self.pooled}: the ROIAlign backward serves <= 8 "
-                                 "(forward-only passes: <= 16)")
+                raise ValueError(f"MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION {self.pooled}: StandardROIHeads.forward trains at <= 8 "
+                                 "(forward-only passes, and the ROIAlign kernels in both directions: <= 16)")
             if not isinstance(targets, BatchedGT):
                 targets = BatchedGT.from_instances(targets, feat.device)
             append = self.proposal_append_gt

@@ -1190,19 +1190,28 @@ def make_rois(props, prop_count):
     return rois
 
 
-def roi_align_fwd(feat, rois, pooled, scale):
+def roi_align_fwd(feat, rois, pooled, scale, sampling_ratio=0, aligned=True):
+    """``(sampling_ratio, aligned) = (0, True)``: the default entry point; anything else: ``sfod_roi_align_fwd_opt``."""
     B, H, W, C = feat.shape
     R = rois.shape[0]
     out = torch.empty(R, pooled * pooled, C, dtype=feat.dtype, device=feat.device)
-    call("sfod_roi_align_fwd", feat, B, H, W, C, rois, R, pooled, float(scale), out, dt_of(feat))
+    if sampling_ratio == 0 and bool(aligned):
+        call("sfod_roi_align_fwd", feat, B, H, W, C, rois, R, pooled, float(scale), out, dt_of(feat))
+    else:
+        call("sfod_roi_align_fwd_opt", feat, B, H, W, C, rois, R, pooled, float(scale), int(sampling_ratio), int(aligned),
+             out, dt_of(feat))
     return out
 
 
-def roi_align_bwd(dout, rois, feat_shape, pooled, scale, dfeat=None):
+def roi_align_bwd(dout, rois, feat_shape, pooled, scale, dfeat=None, sampling_ratio=0, aligned=True):
     B, H, W, C = feat_shape
     if dfeat is None:
         dfeat = torch.zeros(B, H, W, C, dtype=torch.float32, device=dout.device)
-    call("sfod_roi_align_bwd", dout, B, H, W, C, rois, rois.shape[0], pooled, float(scale), dfeat, dt_of(dout))
+    if sampling_ratio == 0 and bool(aligned):
+        call("sfod_roi_align_bwd", dout, B, H, W, C, rois, rois.shape[0], pooled, float(scale), dfeat, dt_of(dout))
+    else:
+        call("sfod_roi_align_bwd_opt", dout, B, H, W, C, rois, rois.shape[0], pooled, float(scale), int(sampling_ratio),
+             int(aligned), dfeat, dt_of(dout))
     return dfeat
 
 
