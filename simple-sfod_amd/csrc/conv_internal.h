@@ -1,5 +1,5 @@
 // Internal (non-ABI) interface between gemm_conv.hip (the sfod_conv_* entry points) and the
-// halo-patch 3x3 kernels in conv3x3_patch.hip / wgrad3x3_rows.hip.
+// halo-patch 3x3 kernels in conv3x3_patch.hip / wgrad3x3_patch.hip.
 #pragma once
 #include "common.h"
 

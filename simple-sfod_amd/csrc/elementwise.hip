@@ -1770,9 +1770,6 @@ __global__ void k_pack_fc_weight(const float* __restrict__ w, T* __restrict__ ou
   }
 }
 
-extern "C" int sfod_pack_fc_weight(const float* w, void* out, int N, int K, int chw_c, int transpose,
-                                   int dt, void* stream);
-
 // fc1-shaped weights (K = C x PP in (c, p) order in the state dict, (p, c) in the kernels): the naive gather
 // above reads with a stride of PP elements.  These two kernels go through an LDS tile so that both the read
 // (contiguous (c, p) runs of one output row) and the write (contiguous c / contiguous n) are coalesced.

@@ -383,7 +383,11 @@ def test_conv_first_layer_kernel(native, hw):
 
 def test_values_beyond_half_range_are_reported(native):
     """A value that had to be clamped at +-65504 (finite or infinite) raises the library's flag; the trainer polls it at its
-    metrics period (native.check_f16x3_range) -- saturation is loud, not silent.  NaN stays NaN (the finite checks' business)."""
+    metrics period (native.check_f16x3_range) -- saturation is loud, not silent.  NaN stays NaN (the finite checks' business).
+    Every producer of half pairs is driven out of range through its public wrapper (BatchNorm, the weight packers,
+    preprocess, the residual join and the casts of elementwise.hip; stem7x7.hip; conv_first.hip), each seen to report once
+    and then read clear.  The exception is roi_align.hip: ROIAlign reads half pairs (at most 65504 in magnitude) and writes
+    convex combinations of them, so no input of its wrapper makes it clamp -- it is shown silent."""
     dev = torch.device(DEV)
     try:
         native.check_f16x3_range(dev)          # whatever earlier tests left behind
@@ -415,6 +419,39 @@ def test_values_beyond_half_range_are_reported(native):
         native.check_f16x3_range(dev)
     native.roi_align_fwd(fp, rois, 7, 1.0 / 32)                 # pooled values are convex combinations of saturated (in-range)
     native.check_f16x3_range(dev)                               # inputs: nothing left to clamp in that kernel, silent
+
+    # the other producers, each through its public wrapper: seen to report once, then clear
+    def reports(producer):
+        try:
+            native.check_f16x3_range(dev)
+        except FloatingPointError:
+            native.check_f16x3_range(dev)
+        else:
+            pytest.fail(f"{producer} clamped a value and did not report it")
+
+    ones, zeros = torch.ones(8, device=DEV), torch.zeros(8, device=DEV)
+    y = torch.ones(1, 2, 2, 8, device=DEV)                      # BatchNorm: gamma * (1 - 0) * 1 = 1e5
+    native.bn_relu_pool_fwd(y, zeros, ones, ones * 1e5, zeros, False, out_dtype=native.SPLITH_DTYPE)
+    reports("bn_relu_pool_fwd")
+    w = torch.ones(8, 8, device=DEV)                            # weights: a non-finite maximum leaves the tensor unscaled,
+    w[2, 3] = float("inf")                                      # the infinity itself is clamped
+    native.pack_fc_weight(w, native.F16X3)
+    reports("pack_fc_weight")
+    img = torch.full((3, 8, 8), 200, dtype=torch.uint8, device=DEV)      # image: (200 - 0) / 1e-4 = 2e6
+    native.preprocess([img], 8, 8, 8, [0.0, 0.0, 0.0], [1e-4, 1e-4, 1e-4], native.F16X3)
+    reports("preprocess")
+    a = torch.full((8,), 40000.0, device=DEV)                   # pointwise: 40000 + 40000
+    native.add_act(a, a, 1, with_operand=native.SPLITH_DTYPE)
+    reports("add_act")
+    x = torch.zeros(2, 16, 9, 4, device=DEV)                    # stem: the input is split into half pairs inside the kernel
+    x[..., :3] = 1.0e5
+    native.stem7x7(x, native.pack_fc_weight(torch.zeros(64, 160, device=DEV), native.F16X3), torch.zeros(64, device=DEV))
+    reports("stem7x7")
+    xd = to_pairs(native, torch.zeros(2, 50, 70, 8, device=DEV))         # first VGG layer: relu(scale * conv + shift), shift = 1e5
+    wp = native.pack_conv_weight(torch.ones(64, 3, 3, 3, device=DEV), 8, native.F16X3)
+    z64 = torch.zeros(64, device=DEV)
+    native.conv_first_apply(xd, wp, z64, z64 + 1.0, z64 + 1.0e5, relu=True)
+    reports("conv_first_apply")
 
 
 @pytest.mark.parametrize("fmt", ["f16", "bf16"])
