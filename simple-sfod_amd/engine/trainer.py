@@ -502,6 +502,10 @@ class BaseTrainer:
         metrics_dict = dict(record_dict)
         metrics_dict["data_time"] = data_time
         self._write_metrics(metrics_dict)
+        self._finish_step(losses)
+
+    def _finish_step(self, losses, ema=True):
+        """the tail of every ``run_step``: backward, gradient exchange, fused update (``ema``: with the teacher's EMA)"""
         self.optimizer.zero_grad()
         with stage("student_backward"):
             try:
@@ -511,7 +515,7 @@ class BaseTrainer:
         with stage("exchange"):
             self._reduce_gradients()
         with stage("update"):
-            self.optimizer.step()
+            self.optimizer.step(ema=ema)
         _step_enqueued(self)
 
     def _reduce_gradients(self):
@@ -973,17 +977,7 @@ class SourceFreeAdaptiveTeacherTrainer(BaseTrainer):
         metrics_dict = dict(loss_dict)
         metrics_dict["data_time"] = data_time
         self._write_metrics(metrics_dict, total=losses.detach())
-        self.optimizer.zero_grad()
-        with stage("student_backward"):
-            try:
-                losses.backward()
-            finally:
-                offchain.clear_loss_grads_mark()      # a mark no head consumed must not meet the next backward
-        with stage("exchange"):
-            self._reduce_gradients()
-        with stage("update"):
-            self.optimizer.step(ema=self.ema_enabled)  # EMA fused: _update_teacher_model (:583-603)
-        _step_enqueued(self)
+        self._finish_step(losses, ema=self.ema_enabled)  # EMA fused: _update_teacher_model (:583-603)
 
     def _flush_metrics(self):
         self.model_teacher.proposal_generator.check_finite()
@@ -1124,17 +1118,7 @@ class AdaptiveTeacherTrainer(SourceFreeAdaptiveTeacherTrainer):
         metrics_dict = dict(record_dict)
         metrics_dict["data_time"] = data_time
         self._write_metrics(metrics_dict)
-        self.optimizer.zero_grad()
-        with stage("student_backward"):
-            try:
-                losses.backward()
-            finally:
-                offchain.clear_loss_grads_mark()
-        with stage("exchange"):
-            self._reduce_gradients()
-        with stage("update"):
-            self.optimizer.step(ema=False)
-        _step_enqueued(self)
+        self._finish_step(losses, ema=False)
 
 
 # ---- AdaBN refinement (base.py:270-337) -----------------------------------------------------------

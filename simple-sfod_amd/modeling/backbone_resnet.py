@@ -31,9 +31,11 @@ import torch
 import torch.nn as nn
 
 from .. import native
-from . import offchain as _offchain
+from .offchain import OffChain
 from ..registry import BACKBONE_REGISTRY
 from ..structures import ShapeSpec
+
+_INLINE = OffChain(False)      # a block's backward called on its own: every launch on the current stream
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -279,7 +281,6 @@ class ResNet(nn.Module):
         """Forward (and, for a backward, rotated) packed weights of every live conv in ONE launch per forward and operand
         format (native.ConvWeightPacker) instead of two tiny launches per conv."""
         key = (dt, bool(with_dgrad))
-        gdt = native.dt_of_dtype(self.grad_dtype)
         packers = self.__dict__.setdefault("_packers", {})
         ent = packers.get(key)
         if ent is None:
@@ -293,16 +294,11 @@ class ResNet(nn.Module):
                             convs.append(c)
             fwd = [(c.weight, c.in_channels, False) for c in convs]
             rot = [(c.weight, c.out_channels, True) for c in convs] if with_dgrad else []
-            if gdt == dt or not rot:
-                pks = (native.ConvWeightPacker(fwd + rot, dt), None)
-            else:
-                pks = (native.ConvWeightPacker(fwd, dt), native.ConvWeightPacker(rot, gdt))
-            ent = packers[key] = (pks, convs)
-        pks, convs = ent
-        views = list(pks[0].pack()) + (list(pks[1].pack()) if pks[1] is not None else [])
-        n = len(convs)
-        self._wp = {id(c): views[i] for i, c in enumerate(convs)}
-        self._wr = {id(c): views[n + i] for i, c in enumerate(convs)} if with_dgrad else {}
+            ent = packers[key] = (native.PackedConvWeights(fwd, rot, dt, native.dt_of_dtype(self.grad_dtype)), convs)
+        pk, convs = ent
+        fwd_w, rot_w = pk.pack()
+        self._wp = {id(c): v for c, v in zip(convs, fwd_w)}
+        self._wr = {id(c): v for c, v in zip(convs, rot_w)}
 
     def _live_conv_bn(self, x, conv, relu, dt, residual=None, z_operand=False, dual=False, z_grad=False, dual_g=False):
         """conv + train-mode BatchNorm (+ ReLU / residual join).  ``x``: an MFMA operand tensor (bf16x3: pairs) or an
@@ -423,8 +419,8 @@ class ResNet(nn.Module):
                 outs[name] = x
         return saved, [outs[n] for n in self._out_features]
 
-    def _conv_bwd(self, g, x_in, y, mean, invstd, conv, relu, need_dx):
-        """grad wrt the norm output -> (dx or None, [dw, dgamma, dbeta])."""
+    def _conv_bwd(self, g, x_in, y, mean, invstd, conv, relu, need_dx, off=_INLINE):
+        """grad wrt the norm output -> (dx or None, [dw, dgamma, dbeta]).  ``off``: the backward's OffChain."""
         bn = conv.norm
         k = conv.kernel_size[0]
         gsink, bsink = native.grad_sink(bn.weight), native.grad_sink(bn.bias)
@@ -435,22 +431,10 @@ class ResNet(nn.Module):
                                                     out_dtype=self.grad_dtype)   # dy only feeds wgrad / dgrad MFMAs
         if direct_bn:
             dgamma = dbeta = None
-        side = self.__dict__.get("_side")
-        if side is not None:
-            # dy is complete on the main stream; the weight gradient reads (x_in, dy) on the side stream while the main
-            # stream goes on with the data gradient.  record_stream keeps the allocator from handing their memory out again
-            # before the side kernel has run, so they need not stay referenced until the join at the end of the backward.
-            ev = torch.cuda.Event()
-            ev.record()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                dw = native.conv_weight_grad(x_in, dy, conv.weight, operand=self.grad_dtype)
-            for t_ in (x_in, dy):
-                if t_ is not None:
-                    t_.record_stream(side)
-            self._side_keep.append(dw)
-        else:
-            dw = native.conv_weight_grad(x_in, dy, conv.weight, operand=self.grad_dtype)
+        # dy is complete on the main stream; the weight gradient reads (x_in, dy) on the side stream while the main
+        # stream goes on with the data gradient.  record_stream keeps the allocator from handing their memory out again
+        # before the side kernel has run, so they need not stay referenced until the join at the end of the backward.
+        dw = off.run(lambda: native.conv_weight_grad(x_in, dy, conv.weight, operand=self.grad_dtype), x_in, dy)
         dx = None
         if need_dx:
             wr = self.__dict__.get("_wr", {}).get(id(conv))      # packed with the forward weights (same step, same values)
@@ -460,19 +444,19 @@ class ResNet(nn.Module):
             dx = native.conv_fwd(dy, wr, None, conv.in_channels, k)
         return dx, [dw, dgamma, dbeta]
 
-    def _block_backward(self, blk, sv, dout, need_dx=True, masked=False, below_out=None):
+    def _block_backward(self, blk, sv, dout, need_dx=True, masked=False, below_out=None, off=_INLINE):
         """dout (grad of the block output, consumed) -> (dx or None, [dw, dgamma, dbeta] per conv, dx already taken
         through the ReLU of the block below).  ``masked``: dout already went through this block's joining ReLU (the
         block above fused it into its own last pass); ``below_out``: output of the block below -- with an identity
         shortcut the sum of the two input-gradient branches and that block's ReLU mask are one pass."""
         (xshape, xs, y1, m1, i1, a1, y2, m2, i2, a2, y3, m3, i3, ys, ms, is_, out) = sv
         g = dout if masked else native.act_bwd_(dout, out, 1)  # through the joining ReLU
-        da2, p3 = self._conv_bwd(g, a2, y3, m3, i3, blk.conv3, False, True)
-        da1, p2 = self._conv_bwd(da2, a1, y2, m2, i2, blk.conv2, True, True)
-        dxs, p1 = self._conv_bwd(da1, xs, y1, m1, i1, blk.conv1, True, need_dx)
+        da2, p3 = self._conv_bwd(g, a2, y3, m3, i3, blk.conv3, False, True, off)
+        da1, p2 = self._conv_bwd(da2, a1, y2, m2, i2, blk.conv2, True, True, off)
+        dxs, p1 = self._conv_bwd(da1, xs, y1, m1, i1, blk.conv1, True, need_dx, off)
         ps = []
         if blk.shortcut is not None:
-            dsc, ps = self._conv_bwd(g, xs, ys, ms, is_, blk.shortcut, False, need_dx)
+            dsc, ps = self._conv_bwd(g, xs, ys, ms, is_, blk.shortcut, False, need_dx, off)
             if need_dx:
                 dxs = native.add_(dxs, dsc)
         elif need_dx:
@@ -490,12 +474,7 @@ class ResNet(nn.Module):
             hook()   # e.g. GradientReducer.launch_early: the heads' gradients are final now
         blocks = self._live_blocks()
         assert len(saved) == len(blocks)
-        self._side, self._side_keep = None, []
-        if self.wgrad_stream and torch.cuda.is_available():
-            st = self.__dict__.get("_side_stream")
-            if st is None:
-                st = self.__dict__["_side_stream"] = _offchain.shared_stream() if _offchain._SHARED else torch.cuda.Stream()
-            self._side = st
+        off = OffChain(self.wgrad_stream and any(g is not None and g.is_cuda for g in out_grads))
         # only the last requested feature feeds the heads on the C4 path; earlier ones would add here
         live_names = [n for n in self.stage_names if n not in self.frozen]
         block_stage = [n for n in live_names for _ in getattr(self, n)]
@@ -522,21 +501,16 @@ class ResNet(nn.Module):
                                                               and block_stage[bi - 1] in gmap):
                 below = saved[bi - 1][-1]
             dx, pg[bi], masked = self._block_backward(blk, saved[bi], dx, need_dx=bi > 0,   # first live block: frozen input
-                                                      masked=masked, below_out=below)
+                                                      masked=masked, below_out=below, off=off)
             saved[bi] = None
             if mid_hook is not None and mid_first == bi:
                 # every gradient of the last live stage is written (weights through the side stream: join it first, so that
                 # the collective, ordered behind the main stream, sees them): GradientReducer.launch_mid
-                if self._side is not None:
-                    torch.cuda.current_stream().wait_stream(self._side)
+                off.wait()
                 mid_hook()
-        if self._side is not None:      # every weight gradient is in its buffer before anyone (all-reduce, SGD, autograd) reads it
-            main = torch.cuda.current_stream()
-            main.wait_stream(self._side)
-            for dw in self._side_keep:      # a gradient tensor made on the side stream is consumed on the main one
-                if dw is not None:
-                    dw.record_stream(main)
-            self._side, self._side_keep = None, []
+        # every weight gradient is in its buffer before anyone (all-reduce, SGD, autograd) reads it; a gradient tensor made
+        # on the side stream is consumed on the main one (handed over in launch order: conv3, conv2, conv1, shortcut)
+        off.join(*(dw for p in pg.values() for dw in p[6::-3] + p[9::3]))
         out = []
         for bi, blk in enumerate(blocks):
             if bi in pg:

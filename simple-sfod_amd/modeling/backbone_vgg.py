@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import native
-from . import offchain as _offchain
+from .offchain import OffChain
 from ..registry import BACKBONE_REGISTRY
 from ..structures import ShapeSpec
 
@@ -200,13 +200,6 @@ class vgg_backbone(nn.Module):
         """Packed forward weights of all layers (+ the rotated dgrad weights of layers 1.. when a backward
         follows), refreshed from the fp32 master weights by ONE launch per call (one per operand format: "f16x3" packs
         the forward weights as half pairs and the rotated ones as bf16 pairs)."""
-        gdt = native.dt_of_dtype(native.grad_dtype_of(native.torch_dtype(dt)))
-        if os.environ.get("SFOD_NO_MULTIPACK"):   # A/B hook: one launch per layer
-            f = [native.pack_conv_weight(c.weight.detach(), cin0_pad if i == 0 else c.in_channels, dt)
-                 for i, (c, _, _, _) in enumerate(self._plan)]
-            r = ([None] + [native.pack_conv_weight(c.weight.detach(), c.out_channels, gdt, rot180=True)
-                           for c, _, _, _ in self._plan[1:]]) if with_dgrad else None
-            return f, r
         key = (dt, cin0_pad, bool(with_dgrad))
         packers = self.__dict__.setdefault("_packers", {})
         pk = packers.get(key)
@@ -214,14 +207,10 @@ class vgg_backbone(nn.Module):
             fwd = [(conv.weight, cin0_pad if li == 0 else conv.in_channels, False)
                    for li, (conv, _, _, _) in enumerate(self._plan)]
             rot = [(conv.weight, conv.out_channels, True) for conv, _, _, _ in self._plan[1:]] if with_dgrad else []
-            if gdt == dt or not rot:
-                pk = (native.ConvWeightPacker(fwd + rot, dt), None)
-            else:
-                pk = (native.ConvWeightPacker(fwd, dt), native.ConvWeightPacker(rot, gdt))
-            packers[key] = pk
-        views = list(pk[0].pack()) + (list(pk[1].pack()) if pk[1] is not None else [])
-        n = len(self._plan)
-        return views[:n], ([None] + list(views[n:]) if with_dgrad else None)
+            gdt = native.dt_of_dtype(native.grad_dtype_of(native.torch_dtype(dt)))
+            pk = packers[key] = native.PackedConvWeights(fwd, rot, dt, gdt)
+        fwd_w, rot_w = pk.pack()
+        return fwd_w, ([None] + rot_w if with_dgrad else None)
 
     def _defer_bn(self, li, y, fwd_w, save, training):
         """May layer ``li``'s BatchNorm + ReLU be left to the next convolution's operand path (sfod_conv_fwd_bnin)?  Only in a
@@ -246,6 +235,11 @@ class vgg_backbone(nn.Module):
         saved, outs = [], []
         fwd_w, rot_w = self._packed_weights(dt, x.shape[-1], save)
         self._rot_w = rot_w
+
+        def finalize(stats, bn, cout, rows):
+            return native.bn_finalize(stats, rows, cout, bn.running_mean, bn.running_var, self.bn_momentum, self.bn_eps,
+                                      self.bn_updates_per_forward, num_batches_tracked=bn.num_batches_tracked)
+
         x_g = native.as_operand(x, self.grad_dtype) if save else None      # conv1_1's weight-gradient operand (8 channels)
         pending = None      # (y, mean, invstd, bn) of the layer below when its BatchNorm + ReLU is left to this layer's conv
         for li, (conv, bn, pool, stage_end) in enumerate(self._plan):
@@ -258,9 +252,7 @@ class vgg_backbone(nn.Module):
                 B, H, W, _ = yb.shape
                 y, stats = native.conv_fwd_bnin(yb, mb, ib, bnb.weight.detach(), bnb.bias.detach(), wp, conv.bias.detach(),
                                                 cout, want_stats=True)
-                mean, invstd = native.bn_finalize(stats, B * H * W, cout, bn.running_mean, bn.running_var,
-                                                  self.bn_momentum, self.bn_eps, self.bn_updates_per_forward,
-                                                  num_batches_tracked=bn.num_batches_tracked)
+                mean, invstd = finalize(stats, bn, cout, B * H * W)
                 if self._defer_bn(li, y, fwd_w, save, training):
                     pending = (y, mean, invstd, bn)
                     continue
@@ -275,18 +267,14 @@ class vgg_backbone(nn.Module):
                 # BatchNorm + ReLU are folded in by recomputation -- a store-free statistics pass, then a second
                 # pass that writes z directly; y (only a backward would need it) is never materialised
                 stats = native.conv_first_stats(x, wp, conv.bias.detach())
-                mean, invstd = native.bn_finalize(stats, B * H * W, cout, bn.running_mean, bn.running_var,
-                                                  self.bn_momentum, self.bn_eps, self.bn_updates_per_forward,
-                                                  num_batches_tracked=bn.num_batches_tracked)
+                mean, invstd = finalize(stats, bn, cout, B * H * W)
                 scale = bn.weight.detach() * invstd
                 shift = bn.bias.detach() - mean * scale
                 x = native.conv_first_apply(x, wp, conv.bias.detach(), scale, shift, relu=True)
                 continue
             if training:
                 y, stats = native.conv_fwd(x, wp, conv.bias.detach(), cout, 3, want_stats=True)
-                mean, invstd = native.bn_finalize(stats, B * H * W, cout, bn.running_mean, bn.running_var,
-                                                  self.bn_momentum, self.bn_eps, self.bn_updates_per_forward,
-                                                  num_batches_tracked=bn.num_batches_tracked)
+                mean, invstd = finalize(stats, bn, cout, B * H * W)
             else:
                 y = native.conv_fwd(x, wp, conv.bias.detach(), cout, 3)
                 mean = bn.running_mean
@@ -323,11 +311,7 @@ class vgg_backbone(nn.Module):
         # weight gradients on a second HIP stream beside the data-gradient chain (the two MFMA kernels of a layer's backward
         # are independent): fills the chip where one kernel's grid does not -- one frame per GPU, the ragged last round of
         # the deep layers (SFOD_VGG_WGRAD_STREAM=0: everything on one stream)
-        side, side_keep = None, []
-        if self.wgrad_stream and dz_dev_is_cuda(out_grads):
-            side = self.__dict__.get("_side_stream")
-            if side is None:
-                side = self.__dict__["_side_stream"] = _offchain.shared_stream() if _offchain._SHARED else torch.cuda.Stream()
+        off = OffChain(self.wgrad_stream and dz_dev_is_cuda(out_grads))
         mid_hook = getattr(self, "_mid_backward", None)
         mid_layer = self._first_layer_of_stage(getattr(self, "_mid_stage", 2)) if mid_hook is not None else -1
         for li in range(len(self._plan) - 1, -1, -1):
@@ -352,22 +336,11 @@ class vgg_backbone(nn.Module):
             if direct_bn:
                 dgamma = dbeta = None
             cout, cin = conv.out_channels, conv.in_channels
-            if side is not None:
-                # dy is complete on the main stream; the weight gradient reads (x, dy) on the side stream while the main one
-                # goes on with the data gradient.  Their memory belongs to the main stream's pool: record_stream tells the
-                # allocator not to hand it out again before the side kernel has run, so the references can be dropped
-                # layer by layer (holding all 13 (x, dy) pairs until the join cost ~180 MB per image and layer at conv1_x)
-                ev = torch.cuda.Event()
-                ev.record()
-                with torch.cuda.stream(side):
-                    side.wait_event(ev)
-                    dw = native.conv_weight_grad(x, dy, conv.weight)
-                for t_ in (x, dy):
-                    if t_ is not None:
-                        t_.record_stream(side)
-                side_keep.append(dw)
-            else:
-                dw = native.conv_weight_grad(x, dy, conv.weight)
+            # dy is complete on the main stream; the weight gradient reads (x, dy) on the side stream while the main one
+            # goes on with the data gradient.  Their memory belongs to the main stream's pool: record_stream tells the
+            # allocator not to hand it out again before the side kernel has run, so the references can be dropped
+            # layer by layer (holding all 13 (x, dy) pairs until the join cost ~180 MB per image and layer at conv1_x)
+            dw = off.run(lambda: native.conv_weight_grad(x, dy, conv.weight), x, dy)
             # a conv bias followed by train-mode BN has an analytically zero gradient
             # (sum_rows dy == 0); the reference's autograd produces rounding noise around 0.
             db = None if native.grad_sink(conv.bias) is not None else torch.zeros_like(conv.bias)
@@ -388,15 +361,10 @@ class vgg_backbone(nn.Module):
                     dz = native.conv_fwd(dy, self._rot_w[li], None, cin, 3)
             del saved[li]
             if li == mid_layer and mid_hook is not None:
-                if side is not None:     # the collective is ordered behind the main stream: the side stream's gradients first
-                    torch.cuda.current_stream().wait_stream(side)
+                off.wait()       # the collective is ordered behind the main stream: the side stream's gradients first
                 mid_hook()   # gradients of vgg2..vgg4 are in the flat buffer: GradientReducer.launch_mid
-        if side is not None:             # every weight gradient is in its buffer before anyone (all-reduce, SGD, autograd) reads it
-            main = torch.cuda.current_stream()
-            main.wait_stream(side)
-            for dw in side_keep:
-                if dw is not None:
-                    dw.record_stream(main)
+        # every weight gradient is in its buffer before anyone (all-reduce, SGD, autograd) reads it; in launch order
+        off.join(*pgrads[::4][::-1])
         return pgrads
 
 

@@ -1,9 +1,8 @@
-"""Parameter-gradient launches of a head's backward beside its data-gradient path (roi_heads.py, rpn.py)."""
+"""Parameter-gradient launches of a backward beside its data-gradient path (both backbones, roi_heads.py, rpn.py)."""
 import os
 
 import torch
 
-_SHARED = os.environ.get("SFOD_SHARED_SIDE_STREAM", "1") != "0"
 _HEAD_WGRAD_STREAM = os.environ.get("SFOD_HEAD_WGRAD_STREAM", "1") != "0"      # 0: everything on one stream (A/B hook)
 
 
@@ -21,44 +20,53 @@ def shared_stream():
     return st
 
 
+def heads_on(t):
+    """the ``on`` of the heads' and the RPN's OffChain: the SFOD_HEAD_WGRAD_STREAM switch, and gradients on a GPU"""
+    return _HEAD_WGRAD_STREAM and t.is_cuda
+
+
 class OffChain:
-    """Parameter-gradient launches of a backward beside its data-gradient path: ``run(fn, *reads)`` executes ``fn`` on the
-    module's side stream once everything enqueued on the current stream so far is done (the tensors in ``reads`` live in the
-    current stream's pool: the allocator is told the side stream uses them); ``join(*outs)`` makes the current stream wait
-    and hands the results over.  Disabled (SFOD_HEAD_WGRAD_STREAM=0, CPU tensors): plain calls."""
+    """Launches of a backward beside its data-gradient path, the ONLY code that moves work to the side stream and back:
+    ``run(fn, *reads)`` executes ``fn`` on the device's side stream once everything enqueued on the current stream so far is
+    done (``after``: once that event is, instead); the tensors in ``reads`` live in the current stream's pool, so the
+    allocator is told the side stream uses them and the caller may drop them before the join.  ``wait()`` makes the current
+    stream wait for the side stream; ``join(*outs)`` does that and hands the results over.  ``on`` false (a caller's A/B
+    switch, CPU tensors): plain calls."""
 
-    def __init__(self, owner, on):
-        self.side = None
-        if on and _HEAD_WGRAD_STREAM:
-            self.side = shared_stream() if _SHARED else owner.__dict__.get("_wgrad_stream")
-            if self.side is None:
-                self.side = owner.__dict__["_wgrad_stream"] = torch.cuda.Stream()
+    def __init__(self, on):
+        self.side = shared_stream() if on else None
 
-    def run(self, fn, *reads):
-        # already ON the side stream (the RPN's whole backward runs there, and its own parameter gradients come through here):
-        # plain calls -- an event recorded on a stream and awaited by the same stream is a no-op eagerly (and a self-dependency
-        # inside a graph capture: what made hipStreamEndCapture crash in round 6's graph experiment)
-        if self.side is None or torch.cuda.current_stream() == self.side:
+    def _beside(self):
+        """already ON the side stream (the RPN's whole backward runs there, and its own parameter gradients come through
+        here): plain calls -- an event recorded on a stream and awaited by the same stream is a no-op eagerly (and a
+        self-dependency inside a graph capture: what made hipStreamEndCapture crash in round 6's graph experiment)"""
+        return self.side is not None and torch.cuda.current_stream() != self.side
+
+    def run(self, fn, *reads, after=None):
+        if not self._beside():
             return fn()
-        ev = torch.cuda.Event()
-        ev.record()
+        if after is None:
+            after = torch.cuda.Event()
+            after.record()
         with torch.cuda.stream(self.side):
-            self.side.wait_event(ev)
+            self.side.wait_event(after)
             out = fn()
         for t_ in reads:
-            t_.record_stream(self.side)
+            if t_ is not None:
+                t_.record_stream(self.side)
         return out
 
+    def wait(self):
+        if self._beside():
+            torch.cuda.current_stream().wait_stream(self.side)
+
     def join(self, *outs):
-        if self.side is None:
-            return
-        main = torch.cuda.current_stream()
-        if main == self.side:
-            return
-        main.wait_stream(self.side)
-        for t_ in outs:
-            if t_ is not None:
-                t_.record_stream(main)
+        if self._beside():
+            self.wait()
+            main = torch.cuda.current_stream()
+            for t_ in outs:
+                if t_ is not None:
+                    t_.record_stream(main)
 
 
 # ---- a whole head's backward beside the other head's --------------------------------------------------------------------
@@ -74,7 +82,7 @@ def mark_loss_grads_ready(g):
     handed to another tensor while the mark exists) and is valid for ONE backward: ``clear_loss_grads_mark`` (the trainers
     call it when ``backward()`` returns) or the first ``take`` drops it."""
     global _loss_grads_ready
-    if _HEAD_WGRAD_STREAM and g.is_cuda:
+    if heads_on(g):
         ev = torch.cuda.Event()
         ev.record()
         _loss_grads_ready = (ev, g, g.device)

@@ -19,7 +19,7 @@ import torch.nn as nn
 from .. import native
 from ..registry import ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY
 from ..structures import Boxes, Instances, ShapeSpec
-from .offchain import OffChain as _OffChain
+from .offchain import OffChain as _OffChain, heads_on as _heads_on
 from .batched import BatchedDetections, BatchedGT, BatchedProposals
 from .box_regression import ROI_DEFAULT_WEIGHTS, roi_box_reg_options
 from .roi_pooler import roi_pooler_options
@@ -346,7 +346,7 @@ class StandardROIHeads(nn.Module):
         NP = self.pred_cols
         d_pred_c = native.cast(d_pred, dtype)
         # predictor: its parameter gradients beside the data-gradient path (``_OffChain``), like fc2's and fc1's below
-        off = _OffChain(self, d_pred.is_cuda)
+        off = _OffChain(_heads_on(d_pred))
         dwp, dbp = off.run(lambda: (native.conv_wgrad(st["h2"], d_pred_c, NP, 1, operand=dtype).view(NP, -1),
                                     native.bias_grad(d_pred, NP)), st["h2"], d_pred_c, d_pred)
         wpt = st.get("wpt")
@@ -368,7 +368,7 @@ class StandardROIHeads(nn.Module):
         C = self.channels
         native.act_bwd_(dh2, st["h2"], 1)
         # fc2
-        off = _OffChain(self, dh2.is_cuda)
+        off = _OffChain(_heads_on(dh2))
         dw2, db2 = off.run(lambda: (native.conv_wgrad(st["h1"], dh2, bh.fc2.out_features, 1, operand=dtype).view(bh.fc2.out_features, -1),
                                     native.bias_grad(dh2, bh.fc2.out_features)), st["h1"], dh2)
         w2t = st.get("w2t")

@@ -18,7 +18,7 @@ from .. import native
 from ..registry import PROPOSAL_GENERATOR_REGISTRY
 from .batched import BatchedGT, BatchedProposals
 from .box_regression import RPN_DEFAULT_WEIGHTS, rpn_box_reg_options
-from .offchain import OffChain, take_loss_grads_ready
+from .offchain import OffChain, heads_on, take_loss_grads_ready
 
 
 class BufferList(nn.Module):
@@ -117,20 +117,9 @@ class _RPNLossFn(torch.autograd.Function):
 
         # beside the ROI heads' backward when the trainer marked where the loss gradients became available (offchain.py)
         ev = take_loss_grads_ready(g_cls)
-        side = OffChain(rpn, g_cls.is_cuda).side if ev is not None else None
-        if side is not None:
-            main = torch.cuda.current_stream()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                dfeat, pgrads = run()
-            for t_ in (g_cls, g_loc):
-                t_.record_stream(side)
-            main.wait_stream(side)
-            for t_ in [dfeat] + list(pgrads):
-                if t_ is not None:
-                    t_.record_stream(main)
-        else:
-            dfeat, pgrads = run()
+        off = OffChain(ev is not None and heads_on(g_cls))
+        dfeat, pgrads = off.run(run, g_cls, g_loc, after=ev)
+        off.join(dfeat, *pgrads)
         ctx.st = ctx.lab_state = None
         return (None, dfeat, None, None, None) + tuple(pgrads)
 
@@ -265,7 +254,7 @@ class RPN(nn.Module):
         t2 = st["t"].view(M, C)
         d_out_c = native.cast(d_out, dtype)
         # 1x1 heads: weight / bias gradients (beside the data-gradient path: ``OffChain``), then data gradient into the hidden map
-        off = OffChain(self, d_out.is_cuda)
+        off = OffChain(heads_on(d_out))
         dw1, db1 = off.run(lambda: (native.conv_wgrad(t2, d_out_c, 5 * A, 1, operand=dtype).view(5 * A, C),
                                     native.bias_grad(d_out, 5 * A)), st["t"], d_out_c, d_out)
         w1t = st.get("w1t")

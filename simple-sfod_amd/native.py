@@ -243,8 +243,6 @@ class KernelTimer:
 
 
 _timer = None
-_pending_flops = 0.0
-_pending_tag = ""
 
 
 def set_timer(timer):
@@ -252,10 +250,10 @@ def set_timer(timer):
     _timer = timer
 
 
-def call(name, *args, timer_name=None):
+def call(name, *args, timer_name=None, flops=0.0, tag=""):
     """Raw call: tensors are converted to device pointers, the current stream is appended.  ``timer_name``: the entry
-    point a KernelTimer files this launch under (sfod_conv_dgrad_bnred runs the sfod_conv_fwd kernel family)."""
-    global _pending_flops
+    point a KernelTimer files this launch under (sfod_conv_dgrad_bnred runs the sfod_conv_fwd kernel family), as
+    "<entry><tag>" with ``flops``, the algorithmic work of THIS launch."""
     lib = load()
     conv = [(_p(a) if isinstance(a, torch.Tensor) else a) for a in args]
     if _timer is not None and (timer_name or name) in _timer.watch:
@@ -263,8 +261,7 @@ def call(name, *args, timer_name=None):
         a.record()
         rc = getattr(lib, name)(*conv, _stream())
         b.record()
-        _timer.records.append(((timer_name or name) + _pending_tag, _pending_flops, a, b))
-        _pending_flops = 0.0
+        _timer.records.append(((timer_name or name) + tag, flops, a, b))
     else:
         rc = getattr(lib, name)(*conv, _stream())
     _chk(rc, name)
@@ -609,6 +606,24 @@ class ConvWeightPacker:
         return self.views
 
 
+class PackedConvWeights:
+    """A module's forward weights and (for a backward) rotated data-gradient weights: ONE ConvWeightPacker when both are
+    packed in the same operand format, two when the gradient format differs ("f16x3": half pairs forward, bf16 pairs
+    rotated) -- one launch per operand format and ``pack()``.  ``rot`` may be empty (forward-only pass)."""
+
+    def __init__(self, fwd, rot, dt, gdt):
+        self.n = len(fwd)
+        if gdt == dt or not rot:
+            self.packers = [ConvWeightPacker(list(fwd) + list(rot), dt)]
+        else:
+            self.packers = [ConvWeightPacker(fwd, dt), ConvWeightPacker(rot, gdt)]
+
+    def pack(self):
+        """-> (forward views, rotated views), each in the order of its specs"""
+        views = [v for pk in self.packers for v in pk.pack()]
+        return views[:self.n], views[self.n:]
+
+
 def unpack_conv_wgrad(dw_packed, dw_oihw, accumulate=False):
     cout, cin, ks, _ = dw_oihw.shape
     call("sfod_unpack_conv_wgrad", dw_packed, dw_oihw, cout, cin, ks, dw_packed.shape[-1], int(accumulate))
@@ -631,6 +646,14 @@ def unpack_fc_wgrad(dw_packed, dw, chw_c=0, accumulate=False):
     call("sfod_unpack_fc_wgrad_ld", dw_packed, dw, n, k, chw_c, dw_packed.shape[-1], int(accumulate))
 
 
+def _stats_buffer(B, H, W, cin, cout, ksize, dt, dev):
+    """BatchNorm partial-statistics buffer of a convolution's epilogue (``.nblk`` rows for bn_finalize)"""
+    nb = query("sfod_conv_stats_blocks", B, H, W, cin, cout, ksize, dt)
+    stats = torch.empty(nb * (2 * cout + 1), dtype=torch.float32, device=dev)
+    stats.nblk = nb
+    return stats
+
+
 def conv_fwd(x, w_packed, bias, cout, ksize, act=0, out_dtype=None, ldy=None, want_stats=False):
     """x [B,H,W,Cin] NHWC (or [R,K] with ksize=1) -> y [B,H,W,ldy]; optional BN partial stats."""
     x = as_operand(x, w_packed.dtype)
@@ -645,26 +668,20 @@ def conv_fwd(x, w_packed, bias, cout, ksize, act=0, out_dtype=None, ldy=None, wa
     ldy = ldy or cout
     alloc = torch.zeros if ldy != cout else torch.empty
     y = alloc(oshape(ldy), dtype=out_dtype, device=x.device)
-    stats = None
-    if want_stats:
-        nb = query("sfod_conv_stats_blocks", B, H, W, cin, cout, ksize, dt)
-        stats = torch.empty(nb * (2 * cout + 1), dtype=torch.float32, device=x.device)
-        stats.nblk = nb
-    global _pending_flops, _pending_tag
-    _pending_flops = 2.0 * B * H * W * cout * ksize * ksize * cin
+    stats = _stats_buffer(B, H, W, cin, cout, ksize, dt, x.device) if want_stats else None
+    flops, tag = 2.0 * B * H * W * cout * ksize * ksize * cin, ""
     if _timer is not None:
-        _pending_tag = ":patch3x3" if query("sfod_conv_fwd_algo", B, H, W, cin, cout, ksize, dt) == 2 else ":gemm"
+        tag = ":patch3x3" if query("sfod_conv_fwd_algo", B, H, W, cin, cout, ksize, dt) == 2 else ":gemm"
     odt = dt_of_dtype(out_dtype)
     # linear layers with few rows (one frame per GPU): the library asks for slab scratch and splits along K
     nscratch = load().sfod_conv_fwd_scratch_bytes(B, H, W, cin, cout, ksize, dt, odt, int(want_stats)) if ksize == 1 else 0
     if nscratch > 0:
         scratch = torch.empty(nscratch, dtype=torch.uint8, device=x.device)
         call("sfod_conv_fwd_scratch", x, w_packed, wscale_of(w_packed), bias, y, B, H, W, cin, cout, ksize, ldy, act, stats,
-             dt, odt, scratch, nscratch, timer_name="sfod_conv_fwd")
+             dt, odt, scratch, nscratch, timer_name="sfod_conv_fwd", flops=flops, tag=tag)
     else:
         call("sfod_conv_fwd_ws", x, w_packed, wscale_of(w_packed), bias, y, B, H, W, cin, cout, ksize, ldy, act, stats, dt,
-             odt, timer_name="sfod_conv_fwd")
-    _pending_tag = ""
+             odt, timer_name="sfod_conv_fwd", flops=flops, tag=tag)
     return (y, stats) if want_stats else y
 
 
@@ -682,19 +699,9 @@ def conv_fwd_bnin(y_pre, mean, invstd, gamma, beta, w_packed, bias, cout, act=0,
     (+ BatchNorm partial statistics), bit-identical to bn_relu_pool_fwd(pairs) followed by conv_fwd."""
     B, H, W, cin = y_pre.shape
     y = torch.empty((B, H, W, cout), dtype=torch.float32, device=y_pre.device)
-    stats = None
-    if want_stats:
-        nb = query("sfod_conv_stats_blocks", B, H, W, cin, cout, 3, BF16X3)
-        stats = torch.empty(nb * (2 * cout + 1), dtype=torch.float32, device=y_pre.device)
-        stats.nblk = nb
-    global _pending_flops, _pending_tag
-    _pending_flops = 2.0 * B * H * W * cout * 9 * cin
-    _pending_tag = ":patch3x3"
-    try:
-        call("sfod_conv_fwd_bnin", y_pre, mean, invstd, gamma, beta, w_packed, bias, y, B, H, W, cin, cout, cout, act, stats,
-             BF16X3, timer_name="sfod_conv_fwd")
-    finally:
-        _pending_tag = ""
+    stats = _stats_buffer(B, H, W, cin, cout, 3, BF16X3, y_pre.device) if want_stats else None
+    call("sfod_conv_fwd_bnin", y_pre, mean, invstd, gamma, beta, w_packed, bias, y, B, H, W, cin, cout, cout, act, stats,
+         BF16X3, timer_name="sfod_conv_fwd", flops=2.0 * B * H * W * cout * 9 * cin, tag=":patch3x3")
     return (y, stats) if want_stats else y
 
 
@@ -708,9 +715,7 @@ def conv_first_supported(x, cout):
 def conv_first_stats(x, w_packed, bias):
     """First VGG layer, pass 1 of the recompute-fused form: BatchNorm partial statistics only, nothing stored."""
     B, H, W, cin = x.shape
-    nb = query("sfod_conv_stats_blocks", B, H, W, cin, 64, 3, dt_of(x))
-    stats = torch.empty(nb * (2 * 64 + 1), dtype=torch.float32, device=x.device)
-    stats.nblk = nb
+    stats = _stats_buffer(B, H, W, cin, 64, 3, dt_of(x), x.device)
     call("sfod_conv_first_fused_ws", x, w_packed, wscale_of(w_packed), bias, None, None, None, stats, B, H, W, 64, 0,
          dt_of(x))
     return stats
@@ -721,7 +726,6 @@ def conv_first_apply(x, w_packed, bias, scale, shift, relu=True):
     pre-BatchNorm output is never stored."""
     B, H, W, cin = x.shape
     z = torch.empty(B, H, W, 64, dtype=x.dtype, device=x.device)
-    global _pending_flops
     call("sfod_conv_first_fused_ws", x, w_packed, wscale_of(w_packed), bias, scale, shift, z, None, B, H, W, 64,
          1 if relu else 0, dt_of(x))
     return z
@@ -759,9 +763,8 @@ def conv_wgrad(x, dy, cout, ksize, dw_packed=None, operand=None):
         dw_packed = torch.zeros(cout_k, ksize * ksize, cin, dtype=torch.float32, device=x.device)
     nbytes = query("sfod_conv_wgrad_ws_bytes", B, H, W, cin, cout_k, ksize, lddy, dt)
     ws = _workspace(x.device, nbytes) if nbytes > 0 else None
-    global _pending_flops
-    _pending_flops = 2.0 * B * H * W * cout * ksize * ksize * cin
-    call("sfod_conv_wgrad", x, dy, dw_packed, B, H, W, cin, cout_k, ksize, lddy, dt, ws, nbytes)
+    call("sfod_conv_wgrad", x, dy, dw_packed, B, H, W, cin, cout_k, ksize, lddy, dt, ws, nbytes,
+         flops=2.0 * B * H * W * cout * ksize * ksize * cin)
     return dw_packed if cout_k == cout else dw_packed[:cout]
 
 
@@ -784,9 +787,8 @@ def conv_wgrad_oihw(x, dy, dw_oihw, accumulate=False):
     dt = dt_of(x)
     nbytes = query("sfod_conv_wgrad_ws_bytes", B, H, W, cin, cout, ksize, lddy, dt)
     ws = _workspace(x.device, nbytes)
-    global _pending_flops
-    _pending_flops = 2.0 * B * H * W * cout * ksize * ksize * cin
-    call("sfod_conv_wgrad_oihw", x, dy, dw_oihw, B, H, W, cin, cout, ksize, lddy, dt, int(accumulate), ws, nbytes)
+    call("sfod_conv_wgrad_oihw", x, dy, dw_oihw, B, H, W, cin, cout, ksize, lddy, dt, int(accumulate), ws, nbytes,
+         flops=2.0 * B * H * W * cout * ksize * ksize * cin)
     return dw_oihw
 
 
@@ -906,14 +908,9 @@ def conv_dgrad_bnred(dy, w_rot, cout, y_below, mean, invstd, gamma, beta):
         return None
     dz = torch.empty(B, H, W, cout, dtype=torch.float32, device=dy.device)
     ws = torch.empty(nb + BN_BWD_SCRATCH_ROWS, 2 * cout, dtype=torch.float32, device=dy.device)   # partial rows + scratch
-    global _pending_flops, _pending_tag
-    _pending_flops = 2.0 * B * H * W * cout * 9 * cin
-    _pending_tag = ":patch3x3"       # the halo-patch kernel with one more epilogue: same roofline line as sfod_conv_fwd's
-    try:
-        call("sfod_conv_dgrad_bnred", dy, w_rot, dz, B, H, W, cin, cout, dt_of(dy), y_below, mean, invstd, gamma, beta,
-             ws, timer_name="sfod_conv_fwd")
-    finally:
-        _pending_tag = ""
+    # the halo-patch kernel with one more epilogue: same roofline line as sfod_conv_fwd's
+    call("sfod_conv_dgrad_bnred", dy, w_rot, dz, B, H, W, cin, cout, dt_of(dy), y_below, mean, invstd, gamma, beta,
+         ws, timer_name="sfod_conv_fwd", flops=2.0 * B * H * W * cout * 9 * cin, tag=":patch3x3")
     return dz, ws
 
 
@@ -983,13 +980,8 @@ def stem7x7(x, w_packed, bias, act=1):
     B, H, W, Cp = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty(B, Ho, Wo, 64, dtype=torch.float32, device=x.device)
-    global _pending_flops, _pending_tag
-    _pending_flops = 2.0 * B * Ho * Wo * 64 * 147
-    if _timer is not None:
-        _pending_tag = ":stem"
     call("sfod_stem7x7", x.contiguous(), w_packed, wscale_of(w_packed), bias, y, B, H, W, Cp, int(act), dt_of_dtype(w_packed.dtype),
-         timer_name="sfod_conv_fwd")
-    _pending_tag = ""
+         timer_name="sfod_conv_fwd", flops=2.0 * B * Ho * Wo * 64 * 147, tag=":stem")
     return y
 
 

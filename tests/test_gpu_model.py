@@ -1158,3 +1158,40 @@ def test_frames_from_pinned_host_memory_give_the_same_batches(sfod, native):
     for ba, bb in zip(*out):
         for (ia, xa, ida), (ib, xb, idb) in zip(ba, bb):
             assert ida == idb and ia.is_cuda and ib.is_cuda and torch.equal(ia, ib) and torch.equal(xa, xb)
+
+
+@pytest.mark.parametrize("yaml,dtype", [(HOT_YAML, "bf16x3"), (R101_YAML, "fp32")], ids=["vgg-bf16x3", "r101-fp32"])
+def test_side_streams_change_no_gradient_bit(sfod, native, monkeypatch, yaml, dtype):
+    """One student loss + backward of the whole model into the flat gradient buffer, from the same seeded state: with every
+    side stream on (the backbone's weight gradients, the heads' parameter gradients, the RPN's backward from the trainer's
+    loss-gradient mark) and with all of them off.  Under ``set_deterministic`` (no float atomics) moving a launch to another
+    stream may change no bit: what differs would be a missing wait or a buffer handed out too early."""
+    oc = sfod.modeling.offchain
+    cfg = make_cfg(sfod, yaml, opts=["SFOD.COMPUTE_DTYPE", dtype])
+    inputs = make_inputs(2, 256, 384, [3, 5], seed=3)
+
+    def flat_grad(streams):
+        torch.manual_seed(3)
+        model = sfod.modeling.build_model(cfg).train()
+        flat = sfod.engine.solver.FlatModelState(model)
+        model.backbone.wgrad_stream = streams
+        monkeypatch.setattr(oc, "_HEAD_WGRAD_STREAM", streams)
+        torch.manual_seed(4)            # the RPN's and the ROI heads' sampling keys
+        losses, _, _, _ = model(inputs, branch="supervised_target", batched=True)
+        keys = sorted(losses)
+        wdev = native.dev_const((1.0,) * len(keys), torch.float32, torch.device(DEV))
+        _, total = sfod.engine.trainer.weighted_loss_sum(wdev, [losses[k] for k in keys])
+        try:
+            total.backward()
+        finally:
+            oc.clear_loss_grads_mark()
+        torch.cuda.synchronize()
+        return flat.grad.clone()
+
+    prev = native.set_deterministic(True)
+    try:
+        on, off = flat_grad(True), flat_grad(False)
+    finally:
+        native.set_deterministic(prev)
+    assert on.abs().sum() > 0 and torch.isfinite(on).all()
+    assert torch.equal(on, off), "max difference {:.3e}".format((on - off).abs().max().item())

@@ -1145,3 +1145,19 @@ def test_bias_grad_in_deterministic_mode_is_the_single_slice_sum_bit_for_bit(nat
             assert np.array_equal(acc.cpu().numpy(), single_slice(x, a.cpu().numpy())), (M, N, ld)
     finally:
         native.set_deterministic(prev)
+
+
+def test_a_flop_count_never_reaches_a_launch_it_does_not_belong_to(native):
+    """KernelTimer annotations travel with their launch (``native.call(..., flops=, tag=)``): a weight gradient computed
+    while no timer is attached leaves nothing behind for the first launch a timer then sees."""
+    x = torch.randn(1, 4, 4, 8, device="cuda")
+    dy = torch.randn(1, 4, 4, 8, device="cuda")
+    native.set_timer(None)
+    native.conv_wgrad(x, dy, 8, 1)
+    timer = native.KernelTimer(watch=None)
+    native.set_timer(timer)
+    try:
+        native.add_(torch.ones(8, device="cuda"), torch.ones(8, device="cuda"))
+    finally:
+        native.set_timer(None)
+    assert [(name, flops) for name, flops, _, _ in timer.records] == [("sfod_add_inplace", 0.0)]

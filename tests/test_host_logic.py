@@ -462,11 +462,15 @@ def test_offchain_helpers_are_plain_calls_without_a_gpu(sfod):
     nor taken -- the heads' backward code paths are the single-stream ones (what the CPU-side oracle comparisons of the
     modules' host logic rely on)."""
     oc = sfod.modeling.offchain
-    off = oc.OffChain(object(), False)
+    off = oc.OffChain(False)
     assert off.side is None
     seen = []
     assert off.run(lambda: (seen.append(1), 7)[1], torch.zeros(2)) == 7 and seen == [1]
+    assert off.run(lambda: (seen.append(2), 8)[1], None, torch.zeros(2), after=None) == 8 and seen == [1, 2]
+    assert off.wait() is None
     off.join(torch.zeros(1), None)
+    assert seen == [1, 2]
+    assert not oc.heads_on(torch.zeros(1))
     g = torch.arange(4.0)
     oc.mark_loss_grads_ready(g)
     assert oc.take_loss_grads_ready(g[1]) is None

@@ -533,11 +533,12 @@ def test_base_trainer_run_step_and_metrics_equal_the_reference(fx, sfod):
     written = {}
     opt = types.SimpleNamespace(n_zero=0, n_step=0, flat=None, grad_scale=1.0)
     opt.zero_grad = lambda: setattr(opt, "n_zero", opt.n_zero + 1)
-    opt.step = lambda: setattr(opt, "n_step", opt.n_step + 1)
+    opt.step = lambda ema=True: setattr(opt, "n_step", opt.n_step + 1)
     model = lambda data: dict(leaves)
     model.training = True
-    stub = types.SimpleNamespace(model=model, optimizer=opt, _data_loader_iter=iter(["batch"]),
-                                 _write_metrics=lambda d, total=None: written.update(d), _reduce_gradients=lambda: None)
+    stub = object.__new__(tr.BaseTrainer)       # (run_step's tail is a method of the class)
+    stub.__dict__.update(model=model, optimizer=opt, _data_loader_iter=iter(["batch"]),
+                         _write_metrics=lambda d, total=None: written.update(d), _reduce_gradients=lambda: None)
     tr.BaseTrainer.run_step(stub)
     got = [float(v.grad) if v.grad is not None else float("nan") for v in leaves.values()]
     assert np.array_equal(np.array(got), fx["bt_grads"], equal_nan=True)

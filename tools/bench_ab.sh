@@ -2,7 +2,7 @@
 # Same-box alternating A/B of bench.py under different environment settings (what the 21 one-off tools/r5_session*.sh of
 # round 5 did by hand; those are in the history at 2886d1a).
 #   bash tools/bench_ab.sh <outdir> <reps> "<bench.py args>" "<ENV=...>" ["<ENV2=... ENV3=...>" ...]
-# e.g. bash tools/bench_ab.sh gpurun_out/ab 2 "--steps 60" "SFOD_SHARED_SIDE_STREAM=1" "SFOD_SHARED_SIDE_STREAM=0"
+# e.g. bash tools/bench_ab.sh bench_outputs/ab 2 "--steps 60" "SFOD_HEAD_WGRAD_STREAM=1" "SFOD_HEAD_WGRAD_STREAM=0"
 #      bash tools/bench_ab.sh gpurun_out/ab 2 "--model r101 --steps 30" "X=1" "SFOD_ROI_NT=0 SFOD_ROI_CBLK=256"
 # Every run: bench.py --no-cpu-baseline --no-secondary --no-kernel-timer <args>; the settings alternate inside each
 # repetition (A B A B ...), the device is given WAIT seconds (default 3; 12 for --res full) to return its memory in between.
