@@ -68,6 +68,21 @@ int sfod_resize_bilinear_u8(const void* src, void* dst, int C, int H, int W, int
                             const int32_t* hbounds, const int32_t* hcoef, int ksize_h,
                             const int32_t* vbounds, const int32_t* vcoef, int ksize_v, int flip,
                             void* stream);
+/* the general form: the whole weak augmentation of one frame -- d2 RandomCrop (INPUT.CROP), ResizeShortestEdge over any
+ * INPUT.MIN_SIZE_TRAIN, RandomFlip horizontal or vertical (d2 build_augmentation; two_crop_augmentation_mapper.py:35-48) --
+ * in one launch and without an intermediate crop tensor:
+ *   dst [C,h,w] = flip(PIL.resize(src[:, y0:y0+ch, x0:x0+cw], (w, h), BILINEAR)),  bit for bit.
+ * src is the whole [C,H,W] frame; the window's rows keep the frame's pitch W.  hbounds/hcoef are the tables for cw -> w,
+ * vbounds/vcoef those for ch -> h (layout as above).  flip_mode: 0 none, 1 horizontal (output column w-1-x), 2 vertical
+ * (output row h-1-y).  h == ch && w == cw is a windowed copy (+ flip), as Pillow returns a copy there: the filter does not
+ * run and the tables are not read.  The kernels' 8-byte tap loads may read bytes outside the window but inside the frame
+ * (weight 0), never outside the frame.  Refused with SFOD_EBADARG before any launch: a window not inside the frame, a
+ * non-positive extent, flip_mode outside {0, 1, 2}, a NULL image or (when the filter runs) table.
+ * sfod_resize_bilinear_u8 is this call with the full window and flip_mode = (flip != 0). */
+int sfod_resize_bilinear_u8_opt(const void* src, void* dst, int C, int H, int W, int y0, int x0, int ch, int cw,
+                                int h, int w, const int32_t* hbounds, const int32_t* hcoef, int ksize_h,
+                                const int32_t* vbounds, const int32_t* vcoef, int ksize_v, int flip_mode,
+                                void* stream);
 
 /* ---- K2/K5/K14/K18: implicit-GEMM convolution / linear layer on MFMA.
  * y[m, n] = act( sum_{tap, c} x[pix(m) + tap][c] * w[n][tap][c] + bias[n] ),  m = (b, oy, ox)

@@ -240,7 +240,12 @@ def get_cfg():
     _C.INPUT.MAX_SIZE_TRAIN = 1333
     _C.INPUT.MIN_SIZE_TEST = 800
     _C.INPUT.MAX_SIZE_TEST = 1333
-    _C.INPUT.RANDOM_FLIP = "horizontal"
+    _C.INPUT.RANDOM_FLIP = "horizontal"     # horizontal | vertical | none (data/weak_augment.py)
+    # d2 T.RandomCrop in front of the resize (two_crop_augmentation_mapper.py:41-48); Detectron2's defaults
+    _C.INPUT.CROP = CN()
+    _C.INPUT.CROP.ENABLED = False
+    _C.INPUT.CROP.TYPE = "relative_range"   # relative | relative_range | absolute | absolute_range
+    _C.INPUT.CROP.SIZE = [0.9, 0.9]
     _C.INPUT.FORMAT = "BGR"
     _C.INPUT.MASK_FORMAT = "polygon"
 

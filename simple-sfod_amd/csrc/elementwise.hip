@@ -171,8 +171,11 @@ extern "C" int sfod_hflip_u8(const void* src, void* dst, int C, int H, int W, vo
 // (22 fractional bits) and a uint8 clip BETWEEN the passes.  Fused here: every output pixel recomputes
 // the <= KS horizontally filtered values of its KS source rows (each rounded and clipped exactly like
 // Pillow's temporary image), then filters them vertically.  The coefficient tables are built on the host
-// (float64, same operation order as Pillow's precompute_coeffs / normalize_coeffs_8bpc).  flip != 0
-// additionally mirrors the output (RandomFlip comes after the resize in the mapper's augmentation list).
+// (float64, same operation order as Pillow's precompute_coeffs / normalize_coeffs_8bpc).
+// The general form is the whole weak augmentation of one frame (d2 RandomCrop -> ResizeShortestEdge -> RandomFlip) in one
+// launch: the source is a WINDOW of the frame (crop: rows keep the frame's pitch W, `woff` = y0 * W + x0 is the window's
+// first byte inside a plane, the tables are built for the window's extents), flip_mode 1 / 2 mirrors the output column / row
+// (RandomFlip comes after the resize in the mapper's augmentation list).
 // ---------------------------------------------------------------------------------------------
 #define RS_PREC 22
 __device__ __forceinline__ int rs_clip8(int v) {
@@ -183,11 +186,14 @@ __device__ __forceinline__ int rs_clip8(int v) {
 // One thread per output pixel (all channels): the horizontal / vertical coefficients are loaded once per
 // pixel, and a source row's <= 8 horizontal taps come in with ONE unaligned 8-byte load (one load per tap,
 // coefficient and channel made the first version 55 loads per output byte: 77 us per 1024x2048 frame).
-template <bool WIDE8>
+// WIN = false is the same body specialised for the default path (the whole frame, horizontal flip or none): woff and the
+// vertical flip fold away at compile time, so that path runs the code it ran before the window existed.
+template <bool WIDE8, bool WIN>
 __global__ void __launch_bounds__(256)
-k_resize_bilinear_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int C, int H, int W,
+k_resize_bilinear_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int C, int H, int W, int64_t woff_arg,
                      int h, int w, const int32_t* __restrict__ hb, const int32_t* __restrict__ hk, int ksh,
                      const int32_t* __restrict__ vb, const int32_t* __restrict__ vk, int ksv, int flip) {
+  const int64_t woff = WIN ? woff_arg : 0;
   const int64_t total = (int64_t)h * w;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
        t += (int64_t)gridDim.x * blockDim.x) {
@@ -195,12 +201,14 @@ k_resize_bilinear_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
     const int y = (int)(t / w);
     const int xmin = hb[2 * x], xn = hb[2 * x + 1];
     const int ymin = vb[2 * y], yn = vb[2 * y + 1];
-    const int xo = flip ? (w - 1 - x) : x;
+    const int xo = (WIN ? flip == 1 : flip != 0) ? (w - 1 - x) : x;
+    const int yo = (WIN && flip == 2) ? (h - 1 - y) : y;
     if constexpr (WIDE8) {
       int kh[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) kh[i] = (i < xn) ? hk[x * ksh + i] : 0;
-      // the 8-byte window must stay inside the plane: shift it left at the right border
+      // the 8-byte load must stay inside the TENSOR (not the crop window: bytes outside the window but inside the frame
+      // may be read and carry weight 0): it is shifted left at the tensor's very end
       const int64_t plane_bytes = (int64_t)H * W;
       if (C == 3 && ksv <= 6) {
         // the common shape (RGB frames, <= 2.5x downscale): all C x ksv row windows are fetched up front (rows beyond
@@ -215,8 +223,10 @@ k_resize_bilinear_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
 #pragma unroll
           for (int j = 0; j < 6; ++j) {
             const int jj = j < yn ? j : (yn > 0 ? yn - 1 : 0);
-            const int64_t off = (int64_t)(ymin + jj) * W + xmin;
-            const int64_t lim = (int64_t)(3 - c) * plane_bytes - 8;       // last legal start in the tensor, from this plane
+            const int64_t off = woff + (int64_t)(ymin + jj) * W + xmin;
+            // INVARIANT: lim is the last legal start of an 8-byte load in the whole [C,H,W] tensor, counted from this
+            // plane -- the end of the tensor, never of the window; nothing is read at or beyond C * H * W
+            const int64_t lim = (int64_t)(3 - c) * plane_bytes - 8;
             const int64_t o2 = off <= lim ? off : lim;
             unsigned long long t8;
             __builtin_memcpy(&t8, src + (int64_t)c * plane_bytes + o2, 8);
@@ -232,7 +242,7 @@ k_resize_bilinear_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
             for (int i = 0; i < 8; ++i) sh += (int)((v[c][j] >> (8 * i)) & 0xffull) * kh[i];
             acc += rs_clip8(sh) * kv[j];
           }
-          dst[((int64_t)c * h + y) * w + xo] = (uint8_t)rs_clip8(acc);
+          dst[((int64_t)c * h + yo) * w + xo] = (uint8_t)rs_clip8(acc);
         }
         continue;
       }
@@ -240,8 +250,9 @@ k_resize_bilinear_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
         const uint8_t* plane = src + (int64_t)c * plane_bytes;
         int acc = 1 << (RS_PREC - 1);
         for (int j = 0; j < yn; ++j) {
-          const int64_t off = (int64_t)(ymin + j) * W + xmin;
-          const int64_t lim = (int64_t)C * plane_bytes - 8 - (int64_t)c * plane_bytes;   // last legal start in the tensor
+          const int64_t off = woff + (int64_t)(ymin + j) * W + xmin;
+          // INVARIANT (as above): the last legal 8-byte start in the TENSOR, from this plane; the window does not enter
+          const int64_t lim = (int64_t)C * plane_bytes - 8 - (int64_t)c * plane_bytes;
           const int64_t o2 = off <= lim ? off : lim;
           const int sh8 = (int)(off - o2) * 8;
           unsigned long long v;
@@ -252,19 +263,19 @@ k_resize_bilinear_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
           for (int i = 0; i < 8; ++i) sh += (int)((v >> (8 * i)) & 0xffull) * kh[i];
           acc += rs_clip8(sh) * vk[y * ksv + j];
         }
-        dst[((int64_t)c * h + y) * w + xo] = (uint8_t)rs_clip8(acc);
+        dst[((int64_t)c * h + yo) * w + xo] = (uint8_t)rs_clip8(acc);
       }
     } else {
       for (int c = 0; c < C; ++c) {
         const uint8_t* plane = src + (int64_t)c * H * W;
         int acc = 1 << (RS_PREC - 1);
         for (int j = 0; j < yn; ++j) {
-          const uint8_t* row = plane + (int64_t)(ymin + j) * W + xmin;
+          const uint8_t* row = plane + woff + (int64_t)(ymin + j) * W + xmin;      // exactly the xn taps: inside the window
           int sh = 1 << (RS_PREC - 1);
           for (int i = 0; i < xn; ++i) sh += (int)row[i] * hk[x * ksh + i];
           acc += rs_clip8(sh) * vk[y * ksv + j];
         }
-        dst[((int64_t)c * h + y) * w + xo] = (uint8_t)rs_clip8(acc);
+        dst[((int64_t)c * h + yo) * w + xo] = (uint8_t)rs_clip8(acc);
       }
     }
   }
@@ -278,12 +289,14 @@ k_resize_bilinear_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
 #define RS_TH 16
 #define RS_TW 64
 #define RS_ROWS 48
+template <bool WIN>      // false: the whole frame, horizontal flip or none (see k_resize_bilinear_u8)
 __global__ void __launch_bounds__(256)
-k_resize_bilinear_u8_tiled(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int W, int h, int w,
+k_resize_bilinear_u8_tiled(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int W, int64_t woff_arg, int h, int w,
                            const int32_t* __restrict__ hb, const int32_t* __restrict__ hk, int ksh,
                            const int32_t* __restrict__ vb, const int32_t* __restrict__ vk, int ksv, int flip,
                            int tiles_x) {
   __shared__ uint8_t tmp[3][RS_ROWS][RS_TW];
+  const int64_t woff = WIN ? woff_arg : 0;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int y0 = ty * RS_TH, x0 = tx * RS_TW;
   const int y1 = min(y0 + RS_TH, h) - 1;
@@ -300,10 +313,12 @@ k_resize_bilinear_u8_tiled(const uint8_t* __restrict__ src, uint8_t* __restrict_
 #pragma unroll
       for (int i = 0; i < 8; ++i) kh[i] = (i < xn) ? hk[x * ksh + i] : 0;
       for (int r = rg; r < nrows; r += 256 / RS_TW) {
-        const int64_t off = (int64_t)(rmin + r) * W + xmin;
+        const int64_t off = woff + (int64_t)(rmin + r) * W + xmin;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          // the 8-byte window must stay inside the tensor: shift it left at the very end (taps beyond carry weight 0)
+          // INVARIANT: the 8-byte load must stay inside the TENSOR -- lim is the last legal start in the whole [3,H,W] frame
+          // from this plane, not the end of the crop window (bytes outside the window but inside the frame are read with
+          // weight 0); the load is shifted left at the tensor's very end (taps beyond carry weight 0)
           const int64_t lim = (int64_t)(3 - c) * plane_bytes - 8;
           const int64_t o2 = off <= lim ? off : lim;
           unsigned long long t8;
@@ -323,22 +338,112 @@ k_resize_bilinear_u8_tiled(const uint8_t* __restrict__ src, uint8_t* __restrict_
     const int xl = threadIdx.x & (RS_TW - 1), rg = threadIdx.x / RS_TW;
     const int x = x0 + xl;
     if (x < w) {
-      const int xo = flip ? (w - 1 - x) : x;
+      const int xo = (WIN ? flip == 1 : flip != 0) ? (w - 1 - x) : x;
       for (int yl = rg; yl < RS_TH; yl += 256 / RS_TW) {
         const int y = y0 + yl;
         if (y >= h) break;
+        const int yo = (WIN && flip == 2) ? (h - 1 - y) : y;
         const int r0 = vb[2 * y] - rmin, yn = vb[2 * y + 1];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           int acc = 1 << (RS_PREC - 1);
           for (int j = 0; j < yn; ++j) acc += (int)tmp[c][r0 + j][xl] * vk[y * ksv + j];
-          dst[((int64_t)c * h + y) * w + xo] = (uint8_t)rs_clip8(acc);
+          dst[((int64_t)c * h + yo) * w + xo] = (uint8_t)rs_clip8(acc);
         }
       }
     }
   }
 }
 
+// Identity scale (output extents == window extents): Pillow returns a copy, so this is a windowed copy (+ flip) and the
+// filter does not run -- "crop without resize", "vertical flip without resize".  16 output bytes per thread; a full chunk is
+// read with two unaligned 8-byte loads that lie inside the window's row (hence inside the tensor), a partial one bytewise.
+__global__ void __launch_bounds__(256)
+k_window_copy_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int C, int H, int W, int64_t woff, int h, int w,
+                 int flip) {
+  const int chunks = (w + 15) / 16;
+  const int64_t total = (int64_t)C * h * chunks;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int ck = (int)(t % chunks);
+    const int64_t r = t / chunks;
+    const int y = (int)(r % h), c = (int)(r / h);
+    const int xs = ck * 16;
+    const int n = min(16, w - xs);
+    const int sx = flip == 1 ? (w - xs - n) : xs;                     // first source column of the chunk
+    const int yo = flip == 2 ? (h - 1 - y) : y;
+    const uint8_t* s = src + (int64_t)c * H * W + woff + (int64_t)y * W + sx;
+    uint8_t* d = dst + ((int64_t)c * h + yo) * w + xs;
+    uint8_t v[16];
+    if (n == 16) {
+      uint8_t u[16];
+      __builtin_memcpy(u, s, 8);
+      __builtin_memcpy(u + 8, s + 8, 8);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = flip == 1 ? u[15 - i] : u[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = (i < n) ? (flip == 1 ? s[n - 1 - i] : s[i]) : (uint8_t)0;
+    }
+    if (n == 16 && ((w & 15) == 0)) {
+      *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(v);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (i < n) d[i] = v[i];
+    }
+  }
+}
+
+extern "C" int sfod_resize_bilinear_u8_opt(const void* src, void* dst, int C, int H, int W, int y0, int x0, int ch, int cw,
+                                           int h, int w, const int32_t* hbounds, const int32_t* hcoef, int ksize_h,
+                                           const int32_t* vbounds, const int32_t* vcoef, int ksize_v, int flip_mode,
+                                           void* stream) {
+  SFOD_REQUIRE_EXTENTS("resize_bilinear_u8_opt", C, H, W, y0, x0, ch, cw, h, w, ksize_h, ksize_v);
+  SFOD_REQUIRE(C >= 1 && H >= 1 && W >= 1 && ch >= 1 && cw >= 1 && h >= 1 && w >= 1,
+               "resize_bilinear_u8_opt: non-positive extent");
+  SFOD_REQUIRE((int64_t)y0 + ch <= H && (int64_t)x0 + cw <= W, "resize_bilinear_u8_opt: the window leaves the frame");
+  SFOD_REQUIRE(flip_mode >= 0 && flip_mode <= 2, "resize_bilinear_u8_opt: flip_mode must be 0 (none), 1 (horizontal) or 2 (vertical)");
+  SFOD_REQUIRE(src != nullptr && dst != nullptr, "resize_bilinear_u8_opt: NULL image");
+  SFOD_REQUIRE(sfod_prod_fits({C, H, W}, 1LL << 40) && sfod_prod_fits({C, h, w}, 1LL << 40) &&
+               sfod_prod_fits({C, H, w}, 1LL << 40), "resize: oversized image");
+  const int64_t woff = (int64_t)y0 * W + x0;
+  hipStream_t s = (hipStream_t)stream;
+  if (h == ch && w == cw) {
+    const int64_t total = (int64_t)C * h * ((w + 15) / 16);
+    hipLaunchKernelGGL(k_window_copy_u8, dim3(ew_grid(total)), dim3(256), 0, s, (const uint8_t*)src, (uint8_t*)dst, C, H, W,
+                       woff, h, w, flip_mode);
+    return sfod_check_launch("resize_bilinear_u8_opt (copy)");
+  }
+  SFOD_REQUIRE(ksize_h >= 1 && ksize_v >= 1, "resize: bad sizes");
+  SFOD_REQUIRE(hbounds != nullptr && hcoef != nullptr && vbounds != nullptr && vcoef != nullptr,
+               "resize_bilinear_u8_opt: NULL coefficient table");
+  // rows a 16-row output tile needs: (its first and last rows' supports) <= 16 * ch / h + ksize_v + 1
+  static const int tiled_on = []() { const char* e = getenv("SFOD_RESIZE_TILED"); return e ? atoi(e) : 1; }();    // A/B hook
+  const int64_t rows_needed = ((int64_t)RS_TH * ch + h - 1) / h + ksize_v + 2;
+  // the whole frame without a vertical flip (the default path, sfod_resize_bilinear_u8): the WIN = false instantiations
+  const bool win = !(woff == 0 && ch == H && cw == W && flip_mode != 2);
+  const uint8_t* sp = (const uint8_t*)src;
+  uint8_t* dp = (uint8_t*)dst;
+  if (tiled_on && C == 3 && ksize_h <= 8 && ksize_v <= 8 && rows_needed <= RS_ROWS && (int64_t)C * H * W >= 8 &&
+      sfod_prod_fits({(h + RS_TH - 1) / RS_TH, (w + RS_TW - 1) / RS_TW})) {
+    const int tiles_x = (w + RS_TW - 1) / RS_TW, tiles_y = (h + RS_TH - 1) / RS_TH;
+    auto k = win ? k_resize_bilinear_u8_tiled<true> : k_resize_bilinear_u8_tiled<false>;
+    hipLaunchKernelGGL(k, dim3(tiles_x * tiles_y), dim3(256), 0, s, sp, dp, H, W, woff, h, w, hbounds, hcoef, ksize_h, vbounds,
+                       vcoef, ksize_v, flip_mode, tiles_x);
+  } else if (ksize_h <= 8 && (int64_t)C * H * W >= 8) {
+    auto k = win ? k_resize_bilinear_u8<true, true> : k_resize_bilinear_u8<true, false>;
+    hipLaunchKernelGGL(k, dim3(ew_grid((int64_t)h * w)), dim3(256), 0, s, sp, dp, C, H, W, woff, h, w, hbounds, hcoef, ksize_h,
+                       vbounds, vcoef, ksize_v, flip_mode);
+  } else {
+    auto k = win ? k_resize_bilinear_u8<false, true> : k_resize_bilinear_u8<false, false>;
+    hipLaunchKernelGGL(k, dim3(ew_grid((int64_t)h * w)), dim3(256), 0, s, sp, dp, C, H, W, woff, h, w, hbounds, hcoef, ksize_h,
+                       vbounds, vcoef, ksize_v, flip_mode);
+  }
+  return sfod_check_launch("resize_bilinear_u8_opt");
+}
+
+// the full window and a horizontal flip or none: the same kernel bodies (their WIN = false instantiations), bit-identical results
 extern "C" int sfod_resize_bilinear_u8(const void* src, void* dst, int C, int H, int W, int h, int w,
                                        const int32_t* hbounds, const int32_t* hcoef, int ksize_h,
                                        const int32_t* vbounds, const int32_t* vcoef, int ksize_v, int flip,
@@ -348,24 +453,8 @@ extern "C" int sfod_resize_bilinear_u8(const void* src, void* dst, int C, int H,
                sfod_prod_fits({C, H, w}, 1LL << 40), "resize: oversized image");
   if ((int64_t)C * h * w == 0) return 0;
   SFOD_REQUIRE(ksize_h >= 1 && ksize_v >= 1 && H >= 1 && W >= 1, "resize: bad sizes");
-  // rows a 16-row output tile needs: (its first and last rows' supports) <= 16 * H / h + ksize_v + 1
-  static const int tiled_on = []() { const char* e = getenv("SFOD_RESIZE_TILED"); return e ? atoi(e) : 1; }();    // A/B hook
-  const int64_t rows_needed = ((int64_t)RS_TH * H + h - 1) / h + ksize_v + 2;
-  if (tiled_on && C == 3 && ksize_h <= 8 && ksize_v <= 8 && rows_needed <= RS_ROWS && (int64_t)C * H * W >= 8 &&
-      sfod_prod_fits({(h + RS_TH - 1) / RS_TH, (w + RS_TW - 1) / RS_TW})) {
-    const int tiles_x = (w + RS_TW - 1) / RS_TW, tiles_y = (h + RS_TH - 1) / RS_TH;
-    hipLaunchKernelGGL(k_resize_bilinear_u8_tiled, dim3(tiles_x * tiles_y), dim3(256), 0, (hipStream_t)stream,
-                       (const uint8_t*)src, (uint8_t*)dst, H, W, h, w, hbounds, hcoef, ksize_h, vbounds, vcoef, ksize_v, flip,
-                       tiles_x);
-  } else if (ksize_h <= 8 && (int64_t)C * H * W >= 8)
-    hipLaunchKernelGGL(k_resize_bilinear_u8<true>, dim3(ew_grid((int64_t)h * w)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint8_t*)src, (uint8_t*)dst, C, H, W, h, w, hbounds, hcoef, ksize_h, vbounds, vcoef,
-                       ksize_v, flip);
-  else
-    hipLaunchKernelGGL(k_resize_bilinear_u8<false>, dim3(ew_grid((int64_t)h * w)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint8_t*)src, (uint8_t*)dst, C, H, W, h, w, hbounds, hcoef, ksize_h, vbounds, vcoef,
-                       ksize_v, flip);
-  return sfod_check_launch("resize_bilinear_u8");
+  return sfod_resize_bilinear_u8_opt(src, dst, C, H, W, 0, 0, H, W, h, w, hbounds, hcoef, ksize_h, vbounds, vcoef, ksize_v,
+                                     flip != 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

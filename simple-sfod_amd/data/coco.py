@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from .synthetic import _resize_u8, resize_shortest_edge_shape
+from .synthetic import _resize_u8, general_weak_augment, resize_shortest_edge_shape
 
 DATASETS = {}      # name -> (json_file, image_root)
 
@@ -115,11 +115,14 @@ def read_image_bgr(path):
 
 class CocoTargetDataset:
     """Same item layout as ``SyntheticTargetDataset`` (image / boxes at the mapper's output scale / classes /
-    native height, width / ids) plus a per-item output ``size``; ``dataset_dicts`` are the loaded records."""
+    native height, width / ids) plus a per-item output ``size``; ``dataset_dicts`` are the loaded records.  Beside them every
+    item keeps a host copy of its native-scale boxes and classes (non-crowd, unfiltered): what the per-iteration mapper of a
+    non-default weak-augmentation option (data/weak_augment.py) starts from; the frames then stay at their native size."""
 
     def __init__(self, cfg, device, names, train=True):
         short = cfg.INPUT.MIN_SIZE_TRAIN[0] if train else cfg.INPUT.MIN_SIZE_TEST
         max_size = cfg.INPUT.MAX_SIZE_TRAIN if train else cfg.INPUT.MAX_SIZE_TEST
+        general = general_weak_augment(cfg, device, train)
         self.device_resize = bool(cfg.SFOD.SYNTHETIC.DEVICE_RESIZE and torch.device(device).type == "cuda")
         self.items, self._dicts, self.class_names = [], [], None
         for name in names:
@@ -162,11 +165,13 @@ class CocoTargetDataset:
 
         for rec, img in decoded_in_order():
             h, w = int(img.shape[1]), int(img.shape[2])
-            newh, neww = resize_shortest_edge_shape(h, w, short, max_size)
-            if (newh, neww) != (h, w) and not self.device_resize:
+            newh, neww = resize_shortest_edge_shape(h, w, short, max_size) if short > 0 else (h, w)
+            if (newh, neww) != (h, w) and not self.device_resize and not general:
                 img = _resize_u8(img, newh, neww)
             # the train mapper drops crowd annotations (two_crop_augmentation_mapper.py:124-131)
             keep = [a for a in rec["annotations"] if a.get("iscrowd", 0) == 0]
+            b64 = np.array([a["bbox"] for a in keep], dtype=np.float64).reshape(-1, 4)
+            native_boxes = np.concatenate([b64[:, :2], b64[:, :2] + b64[:, 2:]], 1)      # XYWH_ABS -> XYXY_ABS in float64, like d2
             b = torch.tensor([a["bbox"] for a in keep], dtype=torch.float32).reshape(-1, 4)
             boxes = torch.cat([b[:, :2], b[:, :2] + b[:, 2:]], 1) * torch.tensor([neww / w, newh / h] * 2)
             boxes[:, 0::2].clamp_(0, neww)          # transform_instance_annotations clips to the image
@@ -175,7 +180,8 @@ class CocoTargetDataset:
             nonempty = ((boxes[:, 2] - boxes[:, 0]) > 1e-5) & ((boxes[:, 3] - boxes[:, 1]) > 1e-5)   # filter_empty_instances
             self.items.append({"image": img.to(device, non_blocking=on_cuda), "boxes": boxes[nonempty].to(device),
                                "classes": classes[nonempty].to(device), "height": h, "width": w,
-                               "image_id": rec["image_id"], "file_name": rec["file_name"], "size": (newh, neww)})
+                               "image_id": rec["image_id"], "file_name": rec["file_name"], "size": (newh, neww),
+                               "boxes_native": native_boxes, "classes_host": classes})
         if on_cuda:
             torch.cuda.synchronize(device)          # the pinned staging buffers may go once every upload has finished
         self.size = self.items[0]["size"] if self.items else (0, 0)

@@ -14,6 +14,11 @@ default); every iteration the mapper's ResizeShortestEdge (shortest 
 Pillow bilinear on uint8) and RandomFlip run on the device in one launch per frame
 (``native.resize_bilinear_u8``, bit-exact with Pillow; SFOD.SYNTHETIC.DEVICE_RESIZE).  On a CPU device
 (host-logic tests) or with DEVICE_RESIZE off the frames are resized once with Pillow at start-up.
+
+With a non-default weak-augmentation option (INPUT.CROP, several MIN_SIZE_TRAIN values or "range" sampling, RANDOM_FLIP
+vertical; ``data/weak_augment.py``) the geometry changes per iteration: the datasets keep the native frame and a host copy of
+the native-scale boxes, and the mapper draws a plan per item -- one ``native.weak_augment_u8`` launch for the image (Pillow on
+a CPU device), Detectron2's float64 box transform on the host.
 """
 import numpy as np
 import torch
@@ -21,21 +26,21 @@ import torch
 from .. import native
 
 from ..structures import Boxes, Instances
+from .weak_augment import WeakAugmentOptions, apply_host, resize_shortest_edge_shape, transform_boxes  # noqa: F401
 
 CITYSCAPES_CLASSES = ["person", "rider", "car", "truck", "bus", "train", "motorcycle", "bicycle"]
 
 
-def resize_shortest_edge_shape(h, w, short, max_size):
-    """d2 ResizeShortestEdge.get_output_shape."""
-    scale = short * 1.0 / min(h, w)
-    if h < w:
-        newh, neww = short, scale * w
-    else:
-        newh, neww = scale * h, short
-    if max(newh, neww) > max_size:
-        scale = max_size * 1.0 / max(newh, neww)
-        newh, neww = newh * scale, neww * scale
-    return int(newh + 0.5), int(neww + 0.5)
+def general_weak_augment(cfg, device, train):
+    """-> True when a training dataset must keep native frames and native-scale boxes for the per-iteration mapper (a
+    non-default weak-augmentation option is active).  On a CUDA device that mapper is the device kernel: asking for the
+    start-up Pillow resize (SFOD.SYNTHETIC.DEVICE_RESIZE False) at the same time is refused, not silently overridden."""
+    if not train or WeakAugmentOptions(cfg).default:
+        return False
+    if torch.device(device).type == "cuda" and not cfg.SFOD.SYNTHETIC.DEVICE_RESIZE:
+        raise ValueError("SFOD.SYNTHETIC.DEVICE_RESIZE False (resize once at start-up) cannot serve INPUT.CROP / multi-scale "
+                         "INPUT.MIN_SIZE_TRAIN / INPUT.RANDOM_FLIP vertical on a CUDA device: the geometry changes per iteration")
+    return True
 
 
 def make_frame(index, height, width, num_boxes, seed=42, num_classes=8):
@@ -74,15 +79,17 @@ class SyntheticTargetDataset:
     def __init__(self, cfg, device, num_images=None, train=True):
         s = cfg.SFOD.SYNTHETIC
         n = num_images or s.NUM_IMAGES
+        general = general_weak_augment(cfg, device, train)
         short = cfg.INPUT.MIN_SIZE_TRAIN[0] if train else cfg.INPUT.MIN_SIZE_TEST
         max_size = cfg.INPUT.MAX_SIZE_TRAIN if train else cfg.INPUT.MAX_SIZE_TEST
-        newh, neww = resize_shortest_edge_shape(s.HEIGHT, s.WIDTH, short, max_size)
-        resize = (newh, neww) != (s.HEIGHT, s.WIDTH)
+        newh, neww = resize_shortest_edge_shape(s.HEIGHT, s.WIDTH, short, max_size) if short > 0 else (s.HEIGHT, s.WIDTH)
+        resize = (newh, neww) != (s.HEIGHT, s.WIDTH) and not general      # general: the mapper works from the native frame
         # resize per iteration on the device (the mapper's job), or once here with Pillow
-        self.device_resize = bool(resize and s.DEVICE_RESIZE and torch.device(device).type == "cuda")
+        self.device_resize = bool((resize or general) and s.DEVICE_RESIZE and torch.device(device).type == "cuda")
         self.items = []
         for i in range(n):
             img, boxes, classes = make_frame(i, s.HEIGHT, s.WIDTH, s.BOXES_PER_IMAGE, seed=max(cfg.SEED, 0))
+            native_boxes = boxes.numpy().astype(np.float64)            # host copy at native scale (data/weak_augment.py)
             if resize:
                 if not self.device_resize:
                     img = _resize_u8(img, newh, neww)
@@ -90,7 +97,8 @@ class SyntheticTargetDataset:
             host = bool(s.get("HOST_FRAMES", False)) and self.device_resize and train      # (the training mapper uploads; section 6)
             self.items.append({"image": img.pin_memory() if host else img.to(device), "boxes": boxes.to(device), "classes": classes.to(device),
                                "height": s.HEIGHT, "width": s.WIDTH, "image_id": i,
-                               "file_name": f"synthetic/{i:06d}.png"})
+                               "file_name": f"synthetic/{i:06d}.png",
+                               "boxes_native": native_boxes, "classes_host": classes.clone()})
         self.size = (newh, neww)
 
     def __len__(self):
@@ -197,6 +205,8 @@ class TwoCropLoader:
         if "ASPECT_RATIO_GROUPING" in cfg.DATALOADER and not cfg.DATALOADER.ASPECT_RATIO_GROUPING and not labeled:
             raise NotImplementedError("ASPECT_RATIO_GROUPING = False is not supported yet")        # build.py:367
         self.batch = total // world
+        self.weak = WeakAugmentOptions(cfg)        # validates INPUT.{RANDOM_FLIP, MIN_SIZE_TRAIN*, CROP.*}: ValueError naming the key
+        self.device = torch.device(device)
         if dataset is None:
             from .coco import build_dataset
             names = cfg.DATASETS.TRAIN if labeled else (cfg.DATASETS.TRAIN_TARGET if "TRAIN_TARGET" in cfg.DATASETS
@@ -216,6 +226,8 @@ class TwoCropLoader:
             self.strong_aug = StrongAugmentation(torch.Generator().manual_seed(max(cfg.SEED, 0) + 7919 * (rank + 1)))
 
     def _map(self, item):
+        if not self.weak.default:
+            return self._map_plan(item, self.weak.sample(int(item["height"]), int(item["width"]), self.gen))
         img, boxes = item["image"], item["boxes"]
         do_flip = bool(self.flip and torch.rand(1, generator=self.gen).item() < 0.5)
         newh, neww = item.get("size", self.dataset.size)
@@ -233,6 +245,36 @@ class TwoCropLoader:
         inst.gt_classes = item["classes"]
         return {"image": img, "instances": inst, "height": item["height"], "width": item["width"],
                 "image_id": item["image_id"], "file_name": item["file_name"]}
+
+    def _map_plan(self, item, plan):
+        """One item under a drawn plan (a non-default weak-augmentation option): the image is ONE launch on the loader's stream
+        (crop + resize + flip), the boxes go through Detectron2's float64 transform on the host and reach the device through
+        pinned memory (no host sync).  The plan travels with the item (``weak_plan``)."""
+        img = item["image"]
+        if "boxes_native" not in item:
+            raise ValueError("INPUT.CROP / multi-scale INPUT.MIN_SIZE_TRAIN / INPUT.RANDOM_FLIP vertical need a dataset that keeps "
+                             "native-scale boxes (boxes_native, classes_host): build it with the same cfg")
+        if tuple(img.shape[1:]) != tuple(plan.native_hw):
+            raise ValueError("the dataset's frames are not at their native size: build it with the same cfg as the loader")
+        on_cuda = self.device.type == "cuda"
+        noop = plan.window is None and plan.flip_mode == 0 and tuple(plan.out_hw) == tuple(plan.native_hw)
+        if on_cuda:
+            if not img.is_cuda:        # SFOD.SYNTHETIC.HOST_FRAMES: the whole frame is uploaded, on the loader's stream
+                img = img.to(self.device, non_blocking=True)
+            if not noop:
+                img = native.weak_augment_u8(img, plan.window, plan.out_hw, plan.flip_mode)
+        elif not noop:
+            img = apply_host(img, plan)
+        b32, keep = transform_boxes(item["boxes_native"], plan)
+        boxes, classes = torch.from_numpy(b32), item["classes_host"][torch.from_numpy(keep)]
+        if on_cuda:
+            boxes = boxes.pin_memory().to(self.device, non_blocking=True)
+            classes = classes.pin_memory().to(self.device, non_blocking=True)
+        inst = Instances((int(img.shape[1]), int(img.shape[2])))
+        inst.gt_boxes = Boxes(boxes)
+        inst.gt_classes = classes
+        return {"image": img, "instances": inst, "height": item["height"], "width": item["width"],
+                "image_id": item["image_id"], "file_name": item["file_name"], "weak_plan": plan}
 
     def __iter__(self):
         return self

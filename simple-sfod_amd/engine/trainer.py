@@ -421,7 +421,9 @@ class BaseTrainer:
             # ``_mid_backward`` there (VGG: the deep stages once vgg<s> is done; ResNet-C4: res4 once its first block is done)
             total = cfg.SOLVER.IMS_PER_BATCH if type(self) is BaseTrainer else cfg.SOLVER.IMS_PER_BATCH_TARGET
             b_local = max(1, int(total) // get_world_size())
-            short = min(cfg.INPUT.MIN_SIZE_TRAIN) if len(cfg.INPUT.MIN_SIZE_TRAIN) else 600
+            # (multi-scale training: the smallest short edge; 0 = "no resize" says nothing about the size)
+            sizes = [int(v) for v in cfg.INPUT.MIN_SIZE_TRAIN if int(v) > 0]
+            short = min(sizes) if sizes else 600
             bb = self.model.backbone
             mids = tuple(bb.reduce_schedule(b_local * short * short * 2)) if hasattr(bb, "reduce_schedule") else ()
             # (this branch runs only when the domain classifier contributes no gradient: its slots stay zero everywhere)

@@ -7,6 +7,7 @@ load, importing any compute entry point raises -- the product path fails loudly.
 PyTorch is used here only as the owner of device memory and streams (``tensor.data_ptr()``,
 ``torch.cuda.current_stream()``).
 """
+import collections
 import ctypes
 import os
 import re
@@ -431,7 +432,55 @@ def pil_bilinear_coeffs(in_size, out_size):
     return bounds, kk, ksize
 
 
-_resize_tabs = {}
+def pil_bilinear_coeffs_np(in_size, out_size):
+    """``pil_bilinear_coeffs`` without the Python double loop: numpy float64, the same operations in the same order (the
+    weights' sum runs tap by tap like the loop's), so the integers are equal (tests/test_weak_augment_host.py).  With
+    INPUT.CROP nearly every frame brings a new (in, out) pair per axis, and the table sits on the loader's critical path."""
+    import math
+    import numpy as np
+    scale = float(in_size) / float(out_size)
+    filterscale = scale if scale >= 1.0 else 1.0
+    support = 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)      # C double -> int: truncation (operand > -1)
+    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    a = np.abs(((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss)
+    k = np.where((a < 1.0) & (x < xmax[:, None]), 1.0 - a, 0.0)
+    ww = np.zeros(out_size, dtype=np.float64)
+    for i in range(ksize):                       # sequential like the loop's ww += w (zeros beyond xmax change nothing)
+        ww = ww + k[:, i]
+    k = np.where(ww[:, None] != 0.0, k / np.where(ww != 0.0, ww, 1.0)[:, None], k)
+    v = k * float(1 << 22)
+    kk = np.where(k < 0, np.trunc(v - 0.5), np.trunc(v + 0.5)).astype(np.int32)
+    bounds = np.stack([xmin, xmax], axis=1).astype(np.int32)
+    return bounds, kk, ksize
+
+
+# (device, stream, in, out) -> (bounds, coeffs, ksize) of ONE axis on the device: rows and columns share entries, and the
+# cache is bounded (least recently used goes first) -- with INPUT.CROP the shapes never stop coming.  Per stream, like the
+# workspaces below: an evicted table's memory returns to the allocator in the order of the stream that allocated and read it.
+_RESIZE_TABS_MAX = 512
+_resize_tabs = collections.OrderedDict()
+
+
+def _axis_tabs(device, in_size, out_size):
+    import numpy as np
+    key = (device, _stream(), int(in_size), int(out_size))
+    tabs = _resize_tabs.get(key)
+    if tabs is not None:
+        _resize_tabs.move_to_end(key)
+        return tabs
+    bounds, kk, ksize = pil_bilinear_coeffs_np(in_size, out_size)
+    both = torch.from_numpy(np.concatenate([bounds.ravel(), kk.ravel()])).to(device)       # one upload per axis
+    n = bounds.size
+    tabs = (both[:n], both[n:], ksize)
+    _resize_tabs[key] = tabs
+    while len(_resize_tabs) > _RESIZE_TABS_MAX:
+        _resize_tabs.popitem(last=False)
+    return tabs
 
 
 def resize_bilinear_u8(img, newh, neww, flip=False):
@@ -440,16 +489,35 @@ def resize_bilinear_u8(img, newh, neww, flip=False):
     assert img.dtype == torch.uint8 and img.dim() == 3
     img = img.contiguous()
     C, H, W = img.shape
-    key = (img.device, H, W, newh, neww)
-    tabs = _resize_tabs.get(key)
-    if tabs is None:
-        hb, hk, ksh = pil_bilinear_coeffs(W, neww)
-        vb, vk, ksv = pil_bilinear_coeffs(H, newh)
-        tabs = tuple(torch.from_numpy(a).to(img.device) for a in (hb, hk, vb, vk)) + (ksh, ksv)
-        _resize_tabs[key] = tabs
-    hb, hk, vb, vk, ksh, ksv = tabs
+    hb, hk, ksh = _axis_tabs(img.device, W, neww)
+    vb, vk, ksv = _axis_tabs(img.device, H, newh)
     out = torch.empty(C, newh, neww, dtype=torch.uint8, device=img.device)
     call("sfod_resize_bilinear_u8", img, out, C, H, W, newh, neww, hb, hk, ksh, vb, vk, ksv, int(flip))
+    return out
+
+
+FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 0, 1, 2
+
+
+def weak_augment_u8(img, window, out_hw, flip_mode, out=None):
+    """The weak augmentation of one uint8 [C,H,W] device frame in one launch (sfod_resize_bilinear_u8_opt):
+    ``flip(PIL.resize(img[:, y0:y0+ch, x0:x0+cw], (w, h), BILINEAR))``, bit for bit.  ``window`` = (y0, x0, ch, cw) or None
+    (the whole frame), ``out_hw`` = (h, w), ``flip_mode`` 0 none / 1 horizontal / 2 vertical.  Output extents equal to the
+    window's: a windowed copy (+ flip), no tables.  Bad windows / modes are refused by the library (NativeLibraryError)."""
+    assert img.dtype == torch.uint8 and img.dim() == 3
+    img = img.contiguous()
+    C, H, W = img.shape
+    y0, x0, ch, cw = (0, 0, H, W) if window is None else (int(v) for v in window)
+    h, w = int(out_hw[0]), int(out_hw[1])
+    if (h, w) == (ch, cw) or min(ch, cw, h, w) < 1:          # (non-positive extents: the library's refusal, not a table error)
+        hb = hk = vb = vk = None
+        ksh = ksv = 1
+    else:
+        hb, hk, ksh = _axis_tabs(img.device, cw, w)
+        vb, vk, ksv = _axis_tabs(img.device, ch, h)
+    if out is None:
+        out = torch.empty(C, max(h, 0), max(w, 0), dtype=torch.uint8, device=img.device)
+    call("sfod_resize_bilinear_u8_opt", img, out, C, H, W, y0, x0, ch, cw, h, w, hb, hk, ksh, vb, vk, ksv, int(flip_mode))
     return out
 
 
@@ -1049,10 +1117,12 @@ def segmented_sort_desc(keys):
     B, n = keys.shape
     dev = keys.device
     nbytes = query("sfod_sort_ws_bytes", B, n)
-    k = (dev, _stream(), nbytes)      # per stream: the teacher's side stream and the main stream may both sort
-    if k not in _sort_ws:
-        _sort_ws[k] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    ws = _sort_ws[k]
+    # per stream: the teacher's side stream and the main stream may both sort.  Grow-only (not one buffer per size): with
+    # multi-scale / cropped training frames (data/weak_augment.py) the sizes change from step to step
+    k = (dev, _stream())
+    ws = _sort_ws.get(k)
+    if ws is None or ws.numel() < nbytes:
+        ws = _sort_ws[k] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out_keys = torch.empty_like(keys)
     out_idx = torch.empty(B, n, dtype=torch.int32, device=dev)
     call("sfod_segmented_sort_desc", keys, B, n, out_keys, out_idx, ws, nbytes)
@@ -1077,10 +1147,10 @@ def nms(boxes, thr, max_keep, valid=None, n_per_image=None, alt_boxes=None, clas
     B, n, _ = boxes.shape
     dev = boxes.device
     nbytes = max(8, query("sfod_nms_mask_bytes", B, n))
-    k = (dev, _stream(), nbytes)      # per stream: two streams may run NMS at once
-    if k not in _mask_ws:
-        _mask_ws[k] = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
-    mask = _mask_ws[k]
+    k = (dev, _stream())              # per stream: two streams may run NMS at once; grow-only, like the sort's
+    mask = _mask_ws.get(k)
+    if mask is None or mask.numel() * 8 < nbytes:
+        mask = _mask_ws[k] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
     keep_idx = torch.zeros(B, max_keep, dtype=torch.int32, device=dev)
     keep_count = torch.zeros(B, dtype=torch.int32, device=dev)
     call("sfod_nms", boxes, alt_boxes, classes, mode, valid, n_per_image, B, n, float(thr), max_keep, mask,
