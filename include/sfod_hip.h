@@ -113,7 +113,11 @@ int sfod_conv_fwd_scratch(const void* x, const void* w, const uint32_t* w_absmax
                           int W, int Cin, int Cout, int ksize, int ldy, int act, float* stats, int dt, int out_dt,
                           void* scratch, int64_t scratch_bytes, void* stream);
 /* number of statistics blocks nblk sfod_conv_fwd writes for this layer shape; `stats` holds
- * nblk * (2*Cout + 1) floats */
+ * nblk * (2*Cout + 1) floats.  The query sees neither ldy nor out_dt: it answers for dense rows (ldy = Cout) and the
+ * operands' own output type (fp32 for operand pairs).  A launch with stats != NULL whose real ldy / out_dt select a kernel
+ * that writes another number of blocks -- a bf16 first layer (Cin 8 -> 64) written as fp32 or with ldy % 8 != 0 runs the
+ * generic kernel instead of the first-layer one -- returns SFOD_EBADARG before anything is launched, with a
+ * sfod_last_error text that names sfod_conv_stats_blocks. */
 int sfod_conv_stats_blocks(int B, int H, int W, int Cin, int Cout, int ksize, int dt);
 /* kernel selection for 3x3 bf16 convolutions: 0 auto, 1 generic implicit GEMM (im2col chunks
  * DMA'd per tap), 2 halo-patch kernel (input patch staged once per 32-channel slice and reused by
@@ -184,9 +188,10 @@ int sfod_set_conv3x3_m16(int on);
  * (k_wgrad3x3_patch<4, true, true>), 0 the round-2 loop.  0 and 1 give bit-identical results, 2 sums the same products over
  * other pixel tiles (equal to fp32 summation order). */
 int sfod_set_wgrad3x3_pipe(int on);
-/* which kernel sfod_conv_fwd runs for this shape: 1 generic implicit GEMM, 2 halo-patch, 3 first-layer
- * kernel (Cin = one padded 8-channel chunk, Cout = 64), 4 generic implicit GEMM on its 256 x 256 tile (bf16x3 linear
- * layers / 1x1 convolutions with wide outputs) */
+/* which kernel sfod_conv_fwd runs for this shape (dense rows, the operands' own output type, the current
+ * sfod_set_conv_algo / sfod_set_gemm_tile settings): 0 extents not served, 1 generic implicit GEMM, 2 halo-patch, 3
+ * first-layer kernel (Cin = one padded 8-channel chunk, Cout = 64), 4 generic implicit GEMM on its 256 x 256 tile (bf16x3
+ * linear layers / 1x1 convolutions with wide outputs) */
 int sfod_conv_fwd_algo(int B, int H, int W, int Cin, int Cout, int ksize, int dt);
 
 /* dt: SFOD_BF16 (x, w, y bf16) or SFOD_BF16X3 (x, w operand pairs; y: the activated operand pairs of the next layer).

@@ -67,6 +67,37 @@ static inline bool sfod_prod_fits(std::initializer_list<long long> dims, long lo
 }
 #define SFOD_REQUIRE_EXTENTS(what, ...) SFOD_REQUIRE(sfod_ints_ok({__VA_ARGS__}), what ": negative or oversized extent")
 
+// ---- A/B knobs (host).  Every knob selects among kernels that compute the same values, so relaxed atomics are enough.
+#include <atomic>
+#include <limits.h>
+#include <stdlib.h>
+// integer value of an environment variable; `dflt` when it is unset or does not start with a number.  For a knob nobody sets
+// at run time, read it once: `static const int v = sfod_env_int("SFOD_X", 1);`
+static inline int sfod_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  char* end = nullptr;
+  const long v = e ? strtol(e, &end, 10) : 0;
+  return (e && end != e) ? (int)v : dflt;
+}
+// process-wide knob with an sfod_set_* entry point: the environment gives the default (read at the first get), a setter
+// call wins over it (also a concurrent one); `norm` maps either source into the knob's range
+struct SfodKnob {
+  const char* env;
+  int dflt;
+  int (*norm)(int);
+  std::atomic<int> v{INT_MIN};      // INT_MIN: not initialised
+  void set(int x) { v.store(norm(x), std::memory_order_relaxed); }
+  int get() {
+    int cur = v.load(std::memory_order_relaxed);
+    if (cur == INT_MIN) {
+      v.compare_exchange_strong(cur, norm(sfod_env_int(env, dflt)), std::memory_order_relaxed);
+      cur = v.load(std::memory_order_relaxed);
+    }
+    return cur;
+  }
+};
+static inline int sfod_knob_bool(int x) { return x ? 1 : 0; }
+
 typedef __bf16 bf16_t;
 
 __device__ __forceinline__ float to_f32(float v) { return v; }

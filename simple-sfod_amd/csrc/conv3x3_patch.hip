@@ -23,7 +23,6 @@
 #include "conv_internal.h"
 #include <type_traits>
 #include <stdlib.h>
-#include <atomic>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -1303,35 +1302,17 @@ k_conv3x3_m16(P3Args a) {
 // and wins by 7-18 % wherever its 128-channel tiles still fill the chip (>= 512 workgroups).
 // SFOD_P3_VARIANT=1..9 / sfod_set_conv3x3_variant force a shape where the channel counts allow it (A/B, tests): 3 / 4 / 7 /
 // 8 / 9 need physical Cin % 64 == 0, 5..9 operand pairs; elsewhere another kernel runs (sfod_last_conv_kernel names it).
-// process-wide tuning knob for A/B runs and tests (relaxed atomic: a plain word, no ordering needed); -1: not
-// initialised (SFOD_P3_VARIANT or 0 = auto).  It selects among kernels that compute the same values.
-static std::atomic<int> g_p3_variant{-1};
+// Process-wide tuning knob for A/B runs and tests (SFOD_P3_VARIANT or 0 = auto; other values mean 0).
+static SfodKnob g_p3_variant{"SFOD_P3_VARIANT", 0, [](int v) { return (v >= 1 && v <= 9) ? v : 0; }};
+extern "C" int sfod_set_conv3x3_variant(int variant) { g_p3_variant.set(variant); return 0; }
 
-// 16x16x32 form of the 256 x 128 shape for operand pairs (k_conv3x3_m16): -1 not initialised (SFOD_P3_M16, default on)
-static std::atomic<int> g_p3_m16{-1};
-extern "C" int sfod_set_conv3x3_m16(int on) {
-  g_p3_m16.store((on >= 0 && on <= 2) ? on : 1, std::memory_order_relaxed);
-  return 0;
-}
+// 16x16x32 form of the 256 x 128 shape for operand pairs (k_conv3x3_m16): SFOD_P3_M16, default on; 0 off, 1 the 8-wave
+// form, 2 the 4-wave form (co-residency experiments)
+static SfodKnob g_p3_m16{"SFOD_P3_M16", 1, [](int on) { return (on >= 0 && on <= 2) ? on : 1; }};
+extern "C" int sfod_set_conv3x3_m16(int on) { g_p3_m16.set(on); return 0; }
 static int p3_m16_n64_enabled() {
-  static const int on = []() { const char* e = getenv("SFOD_P3_M16_N64"); return e ? atoi(e) : 0; }();
+  static const int on = sfod_env_int("SFOD_P3_M16_N64", 0);
   return on;
-}
-static int p3_m16_enabled() {       // 0 off, 1 the 8-wave form (default), 2 the 4-wave form (SFOD_P3_M16=2: co-residency experiments)
-  int v = g_p3_m16.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* ev = getenv("SFOD_P3_M16");
-    int want = ev ? atoi(ev) : 1, expect = -1;
-    if (want < 0 || want > 2) want = 1;
-    g_p3_m16.compare_exchange_strong(expect, want, std::memory_order_relaxed);
-    v = g_p3_m16.load(std::memory_order_relaxed);
-  }
-  return v;
-}
-
-extern "C" int sfod_set_conv3x3_variant(int variant) {
-  g_p3_variant.store((variant >= 1 && variant <= 9) ? variant : 0, std::memory_order_relaxed);
-  return 0;
 }
 
 // tile shape for a BM-pixel workgroup: maximise covered-output efficiency under TH*TW <= BM and
@@ -1362,15 +1343,8 @@ P3Plan sfod_p3_plan(int B, int H, int W, int Cin, int Cout, int pairs) {
   p.ok = 0;
   p.m16 = 0;
   if (H < 1 || W < 1 || B < 1) return p;
-  int variant = g_p3_variant.load(std::memory_order_relaxed);
-  if (variant < 0) {
-    const char* ev = getenv("SFOD_P3_VARIANT");
-    variant = ev ? atoi(ev) : 0;
-    int expect = -1;
-    g_p3_variant.compare_exchange_strong(expect, variant, std::memory_order_relaxed);   // a concurrent setter wins
-    variant = g_p3_variant.load(std::memory_order_relaxed);
-  }
-  p.m16 = (variant == 5) ? 1 : ((variant == 7 || variant == 8) ? 3 : (variant == 9 ? 4 : (variant == 6 ? 2 : ((variant < 1 || variant > 9) ? p3_m16_enabled() : 0))));
+  int variant = g_p3_variant.get();
+  p.m16 = (variant == 5) ? 1 : ((variant == 7 || variant == 8) ? 3 : (variant == 9 ? 4 : (variant == 6 ? 2 : (variant == 0 ? g_p3_m16.get() : 0))));
   if (variant == 5 || variant == 6) variant = 2;
   if (variant == 7 || variant == 9) variant = 3;        // the 64-channel tile shapes on the 16x16x32 loop (k_conv3x3_m16<.., NWN = 1>)
   if (variant == 8) variant = 4;

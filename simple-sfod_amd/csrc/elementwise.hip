@@ -5,7 +5,6 @@
 // (4 x fp32 or 8 x bf16) so a wavefront covers 1 KiB of contiguous channels per instruction.
 #include "conv_internal.h"
 #include <type_traits>
-#include <atomic>
 #include <stdlib.h>
 
 template <typename T> struct VecT;
@@ -419,7 +418,7 @@ extern "C" int sfod_resize_bilinear_u8_opt(const void* src, void* dst, int C, in
   SFOD_REQUIRE(hbounds != nullptr && hcoef != nullptr && vbounds != nullptr && vcoef != nullptr,
                "resize_bilinear_u8_opt: NULL coefficient table");
   // rows a 16-row output tile needs: (its first and last rows' supports) <= 16 * ch / h + ksize_v + 1
-  static const int tiled_on = []() { const char* e = getenv("SFOD_RESIZE_TILED"); return e ? atoi(e) : 1; }();    // A/B hook
+  static const int tiled_on = sfod_env_int("SFOD_RESIZE_TILED", 1);    // A/B hook
   const int64_t rows_needed = ((int64_t)RS_TH * ch + h - 1) / h + ksize_v + 2;
   // the whole frame without a vertical flip (the default path, sfod_resize_bilinear_u8): the WIN = false instantiations
   const bool win = !(woff == 0 && ch == H && cw == W && flip_mode != 2);
@@ -596,20 +595,9 @@ k_bn_finalize_one(const float* __restrict__ stats, int nblocks, int M, int C, fl
   }
 }
 
-static std::atomic<int> g_bn_finalize_fused{-1};      // -1: not initialised (environment SFOD_BN_FINALIZE_FUSED, default on)
-extern "C" int sfod_set_bn_finalize_fused(int on) {
-  g_bn_finalize_fused.store(on ? 1 : 0);
-  return 0;
-}
-static bool bn_finalize_fused() {
-  int v = g_bn_finalize_fused.load();
-  if (v < 0) {
-    const char* e = getenv("SFOD_BN_FINALIZE_FUSED");
-    v = (e != nullptr && e[0] == '0') ? 0 : 1;
-    g_bn_finalize_fused.store(v);
-  }
-  return v != 0;
-}
+static SfodKnob g_bn_finalize_fused{"SFOD_BN_FINALIZE_FUSED", 1, sfod_knob_bool};      // default on
+extern "C" int sfod_set_bn_finalize_fused(int on) { g_bn_finalize_fused.set(on); return 0; }
+static bool bn_finalize_fused() { return g_bn_finalize_fused.get() != 0; }
 
 extern "C" int sfod_bn_finalize_ws_floats(int C) {
   if (!sfod_prod_fits({BNF_SPLITS * 6, C})) return 0;

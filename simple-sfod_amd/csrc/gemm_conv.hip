@@ -15,7 +15,6 @@
 // feeds the MFMAs.
 #include "conv_internal.h"
 #include <algorithm>
-#include <atomic>
 // Knock-out switches for tools/experiments/gemm_knockout.sh (time floors of k_conv_fwd's pair modes; results wrong by
 // construction, the product build defines none): GEMM_KO_MFMA no MFMAs, GEMM_KO_STORE no output stores (fp32 outputs),
 // GEMM_KO_STATS no BatchNorm partial statistics.
@@ -515,23 +514,6 @@ static inline bool is_bf16_storage(int dt) { return dt == SFOD_BF16 || sfod_is_p
 static inline int phys_ch(int dt, int c) { return sfod_is_pairs(dt) ? 2 * c : c; }
 static inline int split_code(int dt) { return dt == SFOD_BF16X3 ? 1 : (dt == SFOD_F16X3 ? 2 : 0); }
 
-static bool use_patch_kernel(const P3Plan& p, int B, int H, int W, int ksize, int dt) {
-  if (ksize != 3 || !is_bf16_storage(dt) || !p.ok || g_conv_algo == 1) return false;
-  if (g_conv_algo == 2) return true;
-  // with the 256-pixel shapes the halo-patch kernel also wins on small maps (batch 1: the 18x37 RPN head
-  // 0.042 vs 0.071 ms, conv5 0.046 vs 0.071); only degenerate problems stay on the generic kernel
-  return (int64_t)B * p.tiles_y * p.tiles_x * p.tiles_n >= 8;
-}
-
-// first VGG layer: 3 real channels in one 8-wide chunk, 64 outputs; bf16 in / bf16 out, or bf16x3 pairs in / fp32 out
-static bool use_first_kernel(int B, int H, int W, int Cin, int Cout, int ksize, int dt, int ldy, int out_dt) {
-  const bool types = (dt == SFOD_BF16 && out_dt == SFOD_BF16) || (sfod_is_pairs(dt) && out_dt == SFOD_F32);
-  return ksize == 3 && types && Cin == 8 && Cout == 64 && ldy % 8 == 0 &&
-         g_conv_algo != 1 && (int64_t)B * H * W >= 4096;
-}
-
-static bool use_wide_gemm(int M, int Cout, int ks);
-
 // host arithmetic of the conv family runs on int pixel counts (M = B * H * W) and int K (Cin * ksize^2): both must fit
 static inline bool conv_shape_fits(int B, int H, int W, int Cin, int Cout, int ksize) {
   return sfod_ints_ok({B, H, W, Cin, Cout, ksize}) && ksize <= 7 && sfod_prod_fits({B, H, W}) &&
@@ -539,20 +521,143 @@ static inline bool conv_shape_fits(int B, int H, int W, int Cin, int Cout, int k
          sfod_prod_fits({B, H, W, Cin > Cout ? Cin : Cout}, 1LL << 40);
 }
 
+// ---- the one rule behind every forward / data-gradient query and launch -------------------------------------------------
+// Which kernel serves a convolution, on which tiles, with how many statistics blocks and how much scratch: the queries
+// read a plan made under the assumptions they document (conv_query_plan), the launchers one made from their arguments.
+enum ConvKind { CONV_NONE, CONV_FIRST, CONV_PATCH, CONV_GEMM, CONV_GEMM_SPLITK };   // NONE: hostile extents, not served
+// workgroup tile (rows x columns) of k_conv_fwd; the values are the codes of sfod_set_gemm_tile / SFOD_GEMM_TILE.
+// K64 (operand pairs only): 64-byte K stages, so that two or three workgroups share a CU; S4: four stages instead of three
+enum GemmTile { T128x64 = 1, T128x128, T256x128, T256x64, T256x256_K64, T256x128_K64, T128x128_K64, T256x128_K64_S4 };
+struct ConvFwdPlan {
+  ConvKind kind = CONV_NONE;
+  P3Plan p3{};                               // CONV_PATCH
+  GemmTile tile = T128x128; bool ut = false; // CONV_GEMM; ut: every K tile inside one filter tap (k_conv_fwd's UT)
+  int splitk = 0; int64_t scratch_bytes = 0; // split-K pieces (0: shape not split) and the scratch they want, offered or not
+  int stats_blocks = 0, abi_algo = 0;        // BatchNorm statistics blocks the launch writes; sfod_conv_fwd_algo's answer
+  bool bnin_ok = false; int bnred_blocks = 0;    // CONV_PATCH: sfod_conv_fwd_bnin serves it; rows sfod_conv_dgrad_bnred writes
+};
+
+static SfodKnob g_gemm_tile{"SFOD_GEMM_TILE", 0, [](int t) { return (t >= 0 && t <= 8) ? t : 0; }};
+extern "C" int sfod_set_gemm_tile(int tile) { g_gemm_tile.set(tile); return 0; }
+
+// M x K(Cin, physical channels) x Cout on k_conv_fwd: `fp32` operands, or `pairs` (with fp32 output), or bf16
+static GemmTile gemm_tile(int M, int64_t Cin, int Cout, int ks, bool ut, bool fp32, bool pairs) {
+  // a forced shape where it exists (A/B runs, tests): 1..4 need uniform taps, 5..8 operand pairs too
+  const int forced = g_gemm_tile.get();
+  if (ut && forced >= 1 && forced <= (pairs ? 8 : 4)) return (GemmTile)forced;
+  // (9 / 10, round 6: a PERSISTENT form of the 256 x 128 tiles -- one workgroup walking several tiles, its DMA pipeline running
+  // across tile boundaries, statistics scratch behind the stages, epilogue barriers that leave vmcnt alone -- was built, was
+  // bit-identical to 3 / 6 on 20 cases, and ran 15 % / 35 % SLOWER on every ResNet-101-C4 1x1 shape: the cold pipeline
+  // per tile is not what these launches wait for.  Removed; profiles/r6_r101_gemm_floor.txt has the table.)
+  if (Cout <= 64) return T128x64;
+  const int64_t rows256 = (M + 255) / 256;
+  // long-K linear layers with few rows (the student's fc1: 4096 x 25088 -> 1024): 256 x 64 tiles, 8 waves, 3-stage
+  // pipeline -- one 8-wave workgroup per CU instead of one 4-wave one (0.35 -> 0.30 ms; SFOD_GEMM_TALL=0 disables)
+  static const int tall = sfod_env_int("SFOD_GEMM_TALL", 300);
+  if (ut && tall > 0 && ks == 1 && Cin >= 4096 && rows256 * ((Cout + 63) / 64) <= tall) return T256x64;
+  // bf16x3 linear layers / 1x1 convolutions with wide outputs: 256 x 256 tiles (64-byte K stages) when their rounds of
+  // 256 workgroups (one per CU) are filled well enough to beat 256 x 128 (profiles/r2d_bench_gemm.txt).  SFOD_GEMM_WIDE =
+  // 0 never / 2 always: A/B runs.  (A 4-stage form of this pipeline -- three K tiles in flight -- measured the same:
+  // profiles/r3_rejected_experiments.txt)
+  static const int wide = sfod_env_int("SFOD_GEMM_WIDE", 1);
+  if (ut && pairs && wide > 0 && ks == 1 && Cout >= 256) {
+    const int64_t t256 = rows256 * ((Cout + 255) / 256), t128 = rows256 * ((Cout + 127) / 128);
+    const double r256 = (double)((t256 + 255) / 256), r128 = (double)((t128 + 255) / 256) * 0.5;   // rounds, in 256-wide tile times
+    if (wide == 2 || (t256 >= 200 && r256 * 0.80 <= r128)) return T256x256_K64;
+  }
+  // fp32 (MFMA-bound at 1/16 of the bf16 rate: a tile's time is its FLOPs, the operand stream is never the limit): pick
+  // the tile shape by whole-chip rounds.  The ResNet-C4 layers at 600x1200 have few tiles per CU (res4: 22 800 rows x
+  // 256 channels = 358 tiles of 128 x 128 on 256 CUs: two rounds for 1.4 rounds of work); 128 x 64 tiles pack the same
+  // layer into 716 / 768 slots (three per CU) -- cost = ceil(workgroups / 256) x tile area, smaller is better, ties to
+  // the larger tile.  SFOD_GEMM_FP32_TILES=0 restores the fixed rule (A/B).
+  static const int cost_rule = sfod_env_int("SFOD_GEMM_FP32_TILES", 1);
+  if (ut && fp32 && cost_rule) {
+    auto rounds = [&](int bm, int bn) {
+      const int64_t wgs = (int64_t)((M + bm - 1) / bm) * ((Cout + bn - 1) / bn);
+      return (double)((wgs + 255) / 256) * bm * bn;
+    };
+    const double c256 = rounds(256, 128) * 0.98, c128 = rounds(128, 128), c64 = rounds(128, 64) * 1.03;
+    return (c64 < c128 && c64 < c256) ? T128x64 : (c256 <= c128 ? T256x128 : T128x128);
+  }
+  // 256 x 128 tiles with a 3-stage DMA pipeline once the grid still fills the chip (>= 2 tiles / CU)
+  return (ut && rows256 * ((Cout + 127) / 128) >= 384) ? T256x128 : T128x128;
+}
+
+// ldy: row stride of y; scratch_bytes: what the caller offers (0: none)
+static ConvFwdPlan conv_fwd_plan(int B, int H, int W, int Cin, int Cout, int ksize, int dt, int out_dt, int ldy,
+                                 bool with_stats, int64_t scratch_bytes) {
+  ConvFwdPlan p;
+  const bool pairs = sfod_is_pairs(dt);
+  // hostile extents (pairs: the physical channel count is an int as well): not served / nothing
+  if (!conv_shape_fits(B, H, W, Cin, Cout, ksize) || !sfod_prod_fits({Cin, pairs ? 2 : 1})) return p;
+  const int M = B * H * W, pc = phys_ch(dt, Cin), algo = g_conv_algo;
+  // first VGG layer: 3 real channels in one 8-wide chunk, 64 outputs; bf16 in / bf16 out, or operand pairs in / fp32 out
+  const bool first_types = (dt == SFOD_BF16 && out_dt == SFOD_BF16) || (pairs && out_dt == SFOD_F32);
+  if (ksize == 3 && first_types && Cin == 8 && Cout == 64 && ldy % 8 == 0 && algo != 1 && M >= 4096) {
+    p.kind = CONV_FIRST; p.abi_algo = 3; p.stats_blocks = sfod_f1_nblk(B, H, W);
+    return p;
+  }
+  if (ksize == 3 && is_bf16_storage(dt) && algo != 1) {
+    p.p3 = sfod_p3_plan(B, H, W, pc, Cout, pairs);
+    // with the 256-pixel shapes the halo-patch kernel also wins on small maps (batch 1: the 18x37 RPN head
+    // 0.042 vs 0.071 ms, conv5 0.046 vs 0.071); only degenerate problems stay on the generic kernel
+    if (p.p3.ok && (algo == 2 || (int64_t)B * p.p3.tiles_y * p.p3.tiles_x * p.p3.tiles_n >= 8)) {
+      p.kind = CONV_PATCH; p.abi_algo = 2; p.stats_blocks = p.p3.nblk;
+      p.bnin_ok = sfod_p3_bnin_ok(p.p3, pc, split_code(dt));
+      // (bf16 mode writes bf16 gradients: no fp32 tile to reduce; half pairs: forward only)
+      p.bnred_blocks = (dt == SFOD_BF16X3 && Cout % 4 == 0) ? p.p3.nblk : 0;
+      return p;
+    }
+  }
+  const int E = (dt == SFOD_F32) ? 4 : 8;
+  p.kind = CONV_GEMM; p.ut = (ksize == 1) || ((pc / E) % 8 == 0);
+  p.tile = gemm_tile(M, pc, Cout, ksize, p.ut, dt == SFOD_F32, pairs);
+  p.abi_algo = (p.tile == T256x256_K64) ? 4 : 1;
+  p.stats_blocks = (M + 127) / 128;
+  // Split-K for linear layers with few rows.  One frame per GPU (the yaml's literal batch): fc1 of the student is 512 x
+  // 25088 -> 1024 = 32 workgroups of 256 x 64 on 256 CUs, each walking 784 K tiles (0.6 ms for 26 GFLOP).  With the K range
+  // cut in S pieces the grid is S x 32, every piece writes its fp32 partial tile into slab s of the caller's scratch, and
+  // k_splitk_sum adds the slabs in index order (fixed: run-to-run identical) together with bias and activation.  Chosen
+  // only when the plain grid leaves half the chip idle and every piece still has >= 32 of at least 256 K tiles: long K only
+  // (fc1-class layers: >= 256 K tiles = 8192 logical channels in the pair modes) -- a short-K layer with few rows is a 10 us
+  // launch either way, and every split is one more fp32 summation order in the model.
+  static const int splitk_on = sfod_env_int("SFOD_GEMM_SPLITK", 1);
+  const int64_t wgs = (int64_t)((M + 255) / 256) * ((Cout + 63) / 64);
+  const int KT_all = (pc / E + 7) / 8;
+  if (splitk_on && (dt == SFOD_F32 || is_bf16_storage(dt)) && ksize == 1 && out_dt == SFOD_F32 && !with_stats &&
+      Cout % 4 == 0 && Cin % E == 0 && M >= 1 && M <= (1 << 24) && wgs >= 1 && wgs <= 128 && KT_all >= 256) {
+    const int S = (int)std::min<int64_t>(std::min<int64_t>(256 / wgs, 8), KT_all / 32);
+    if (S >= 2) { p.splitk = S; p.scratch_bytes = (int64_t)S * M * Cout * 4; }
+    if (S >= 2 && scratch_bytes >= p.scratch_bytes) p.kind = CONV_GEMM_SPLITK;      // (launch_splitk has its own tile: 256 x 64)
+  }
+  return p;
+}
+
+// What the queries answer from (include/sfod_hip.h says what each means): dense rows (ldy = Cout), fp32 output for operand
+// pairs and the operand type otherwise.
+static ConvFwdPlan conv_query_plan(int B, int H, int W, int Cin, int Cout, int ksize, int dt) {
+  return conv_fwd_plan(B, H, W, Cin, Cout, ksize, dt, sfod_is_pairs(dt) ? SFOD_F32 : dt, Cout, true, 0);
+}
+
 extern "C" int sfod_conv_fwd_algo(int B, int H, int W, int Cin, int Cout, int ksize, int dt) {
-  if (!conv_shape_fits(B, H, W, Cin, Cout, ksize)) return 0;      // hostile extents: not served / nothing
-  if (use_first_kernel(B, H, W, Cin, Cout, ksize, dt, 64, sfod_is_pairs(dt) ? SFOD_F32 : SFOD_BF16)) return 3;
-  const P3Plan p = (ksize == 3 && is_bf16_storage(dt)) ? sfod_p3_plan(B, H, W, phys_ch(dt, Cin), Cout, sfod_is_pairs(dt)) : P3Plan{};
-  if (use_patch_kernel(p, B, H, W, ksize, dt)) return 2;
-  return (sfod_is_pairs(dt) && use_wide_gemm(B * H * W, Cout, ksize)) ? 4 : 1;     // (fp32 output assumed: bf16x3 has no other)
+  return conv_query_plan(B, H, W, Cin, Cout, ksize, dt).abi_algo;
 }
 
 extern "C" int sfod_conv_stats_blocks(int B, int H, int W, int Cin, int Cout, int ksize, int dt) {
-  if (!conv_shape_fits(B, H, W, Cin, Cout, ksize)) return 0;      // hostile extents: not served / nothing
-  if (use_first_kernel(B, H, W, Cin, Cout, ksize, dt, 64, sfod_is_pairs(dt) ? SFOD_F32 : SFOD_BF16)) return sfod_f1_nblk(B, H, W);
-  const P3Plan p = (ksize == 3 && is_bf16_storage(dt)) ? sfod_p3_plan(B, H, W, phys_ch(dt, Cin), Cout, sfod_is_pairs(dt)) : P3Plan{};
-  if (use_patch_kernel(p, B, H, W, ksize, dt)) return p.nblk;
-  return (B * H * W + 127) / 128;
+  return conv_query_plan(B, H, W, Cin, Cout, ksize, dt).stats_blocks;
+}
+
+extern "C" int64_t sfod_conv_fwd_scratch_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int dt, int out_dt,
+                                               int with_stats) {
+  return conv_fwd_plan(B, H, W, Cin, Cout, ksize, dt, out_dt, Cout, with_stats != 0, 0).scratch_bytes;
+}
+
+extern "C" int sfod_conv_fwd_bnin_supported(int B, int H, int W, int Cin, int Cout, int dt) {
+  return conv_query_plan(B, H, W, Cin, Cout, 3, dt).bnin_ok ? 1 : 0;
+}
+
+extern "C" int sfod_conv_dgrad_bnred_blocks(int B, int H, int W, int Cin, int Cout, int dt) {
+  return conv_query_plan(B, H, W, Cin, Cout, 3, dt).bnred_blocks;
 }
 
 template <typename T, typename OutT, int WN, bool UT, int WR, int NST, int SPLIT = 0, int BKB = 128>
@@ -578,26 +683,6 @@ static int launch_one(const void* x, const void* w, const float* bias, void* y, 
   hipLaunchKernelGGL(kern, dim3(nt, a.kt_per ? a.nsplit : 1), dim3(WR * 128), LDS, s, (const T*)x, (const T*)w, bias, (OutT*)y,
                      stats, a, tiles_n, nt);
   return sfod_check_launch("conv_fwd");
-}
-
-// ---- split-K for linear layers with few rows ----------------------------------------------------------------------------
-// One frame per GPU (the yaml's literal batch): fc1 of the student is 512 x 25088 -> 1024 = 32 workgroups of 256 x 64 on 256
-// CUs, each walking 784 K tiles (0.6 ms for 26 GFLOP).  With the K range cut in S pieces the grid is S x 32, every piece
-// writes its fp32 partial tile into slab s of the caller's scratch, and k_splitk_sum adds the slabs in index order (fixed:
-// run-to-run identical) together with bias and activation.  Chosen only when the plain grid leaves half the chip idle and
-// every piece still has >= 32 of at least 256 K tiles; the scratch is S x M x Cout floats.
-static int splitk_plan(int M, int kchunks, int Cout, int ks, bool fp32_out, bool stats) {
-  static const int on = []() { const char* e = getenv("SFOD_GEMM_SPLITK"); return e ? atoi(e) : 1; }();
-  if (!on || ks != 1 || !fp32_out || stats || M < 1) return 0;
-  const int64_t wgs = (int64_t)((M + 255) / 256) * ((Cout + 63) / 64);
-  const int KT_all = (kchunks + 7) / 8;
-  // long K only (fc1-class layers: >= 256 K tiles = 8192 logical channels in the pair modes): a short-K layer with few rows
-  // is a 10 us launch either way, and every split is one more fp32 summation order in the model
-  if (wgs > 128 || KT_all < 256) return 0;
-  int S = (int)(256 / wgs);
-  if (S > 8) S = 8;
-  if (S > KT_all / 32) S = KT_all / 32;
-  return S >= 2 ? S : 0;
 }
 
 __global__ void __launch_bounds__(256) k_splitk_sum(const float* __restrict__ ws, int S, int64_t slab, int M, int Cout,
@@ -637,107 +722,53 @@ static int launch_splitk(const void* x, const void* w, const float* bias, float*
   return sfod_check_launch("splitk_sum");
 }
 
-// bf16x3, ksize 1, fp32 out: does the 256 x 256 tile serve this shape?  (SFOD_GEMM_WIDE = 0 never / 2 always: A/B runs)
-static bool use_wide_gemm(int M, int Cout, int ks) {
-  static const int wide = []() { const char* e = getenv("SFOD_GEMM_WIDE"); return e ? atoi(e) : 1; }();
-  if (wide <= 0 || ks != 1 || Cout < 256) return false;
-  const int64_t t256 = (int64_t)((M + 255) / 256) * ((Cout + 255) / 256);
-  const int64_t t128 = (int64_t)((M + 255) / 256) * ((Cout + 127) / 128);
-  const double r256 = (double)((t256 + 255) / 256), r128 = (double)((t128 + 255) / 256) * 0.5;   // rounds, in 256-wide tile times
-  return wide == 2 || (t256 >= 200 && r256 * 0.80 <= r128);
-}
-
-// forced tile shape of the generic kernel (A/B runs, tests): -1 not initialised (SFOD_GEMM_TILE or 0 = the planner's choice)
-static std::atomic<int> g_gemm_tile{-1};
-extern "C" int sfod_set_gemm_tile(int tile) {
-  g_gemm_tile.store((tile >= 0 && tile <= 8) ? tile : 0, std::memory_order_relaxed);
-  return 0;
-}
-static int gemm_tile_forced() {
-  int v = g_gemm_tile.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("SFOD_GEMM_TILE");
-    int want = e ? atoi(e) : 0, expect = -1;
-    if (want < 0 || want > 8) want = 0;
-    g_gemm_tile.compare_exchange_strong(expect, want, std::memory_order_relaxed);
-    v = g_gemm_tile.load(std::memory_order_relaxed);
-  }
-  return v;
-}
-
-template <typename T, typename OutT, bool UT, int SPLIT = 0>
-static int launch_conv_fwd_ut(const void* x, const void* w, const float* bias, void* y, float* stats,
-                              const ConvArgs& a, hipStream_t s) {
-  // SFOD_GEMM_TILE = 1..5: force a tile shape where it exists (A/B runs: 1 128x64, 2 128x128, 3 256x128, 4 256x64, 5 256x256)
-  const int forced = gemm_tile_forced();
-  if constexpr (UT) {
-    if (forced == 1) return launch_one<T, OutT, 1, UT, 2, 2, SPLIT>(x, w, bias, y, stats, a, s);
-    if (forced == 2) return launch_one<T, OutT, 2, UT, 2, 2, SPLIT>(x, w, bias, y, stats, a, s);
-    if (forced == 3) return launch_one<T, OutT, 2, UT, 4, 3, SPLIT>(x, w, bias, y, stats, a, s);
-    if (forced == 4) return launch_one<T, OutT, 1, UT, 4, 3, SPLIT>(x, w, bias, y, stats, a, s);
+// GemmTile -> kernel instantiation.  The guards say where a shape is built: without uniform taps the two 128-row shapes
+// (256 x 128 is instantiated there too, though gemm_tile never picks it), 256 x 64 with them, the K64 shapes for operand
+// pairs only.
+template <typename T, typename OutT, bool UT, int SPLIT>
+static int launch_tile(GemmTile tile, const void* x, const void* w, const float* bias, void* y, float* stats,
+                       const ConvArgs& a, hipStream_t s) {
+#define TILE(WN, WR, ...) launch_one<T, OutT, WN, UT, WR, __VA_ARGS__>(x, w, bias, y, stats, a, s)
+  if constexpr (!UT) {
+    switch (tile) {
+      case T128x64: return TILE(1, 2, 2, SPLIT);
+      case T256x128: return TILE(2, 4, 3, SPLIT);
+      case T128x128: return TILE(2, 2, 2, SPLIT);
+      default: break;
+    }
+  } else {
+    switch (tile) {
+      case T128x64: return TILE(1, 2, 2, SPLIT);
+      case T128x128: return TILE(2, 2, 2, SPLIT);
+      case T256x128: return TILE(2, 4, 3, SPLIT);
+      case T256x64: return TILE(1, 4, 3, SPLIT);
+      default: break;
+    }
     if constexpr (SPLIT && sizeof(OutT) == 4) {
-      if (forced == 5) return launch_one<T, OutT, 4, UT, 4, 3, SPLIT, 64>(x, w, bias, y, stats, a, s);
-      // round 6: 64-byte K stages so that TWO workgroups share a CU (their prologues / epilogues / barrier stalls overlap):
-      // 6: 256 x 128, 3 stages (72 KiB); 7: 128 x 128, 3 stages (48 KiB: three per CU); 8: 256 x 128, 4 stages (96 KiB)
-      if (forced == 6) return launch_one<T, OutT, 2, UT, 4, 3, SPLIT, 64>(x, w, bias, y, stats, a, s);
-      if (forced == 7) return launch_one<T, OutT, 2, UT, 2, 3, SPLIT, 64>(x, w, bias, y, stats, a, s);
-      if (forced == 8) return launch_one<T, OutT, 2, UT, 4, 4, SPLIT, 64>(x, w, bias, y, stats, a, s);
-      // (9 / 10, round 6: a PERSISTENT form of this tile -- one workgroup walking several tiles, its DMA pipeline running across
-      // tile boundaries, statistics scratch behind the stages, epilogue barriers that leave vmcnt alone -- was built, was
-      // bit-identical to 3 / 6 on 20 cases, and ran 15 % / 35 % SLOWER on every ResNet-101-C4 1x1 shape: the cold pipeline
-      // per tile is not what these launches wait for.  Removed; profiles/r6_r101_gemm_floor.txt has the table.)
+      switch (tile) {
+        case T256x256_K64: return TILE(4, 4, 3, SPLIT, 64);
+        case T256x128_K64: return TILE(2, 4, 3, SPLIT, 64);        // 72 KiB: two per CU
+        case T128x128_K64: return TILE(2, 2, 3, SPLIT, 64);        // 48 KiB: three per CU
+        case T256x128_K64_S4: return TILE(2, 4, 4, SPLIT, 64);     // 96 KiB
+        default: break;
+      }
     }
   }
-  if (a.Cout <= 64) return launch_one<T, OutT, 1, UT, 2, 2, SPLIT>(x, w, bias, y, stats, a, s);
-  // long-K linear layers with few rows (the student's fc1: 4096 x 25088 -> 1024): 256 x 64 tiles, 8 waves, 3-stage
-  // pipeline -- one 8-wave workgroup per CU instead of one 4-wave one (0.35 -> 0.30 ms; SFOD_GEMM_TALL=0 disables)
-  static const int tall = []() { const char* e = getenv("SFOD_GEMM_TALL"); return e ? atoi(e) : 300; }();
-  if constexpr (UT) {
-    if (tall > 0 && a.ks == 1 && a.Cin >= 4096 && (int64_t)((a.M + 255) / 256) * ((a.Cout + 63) / 64) <= tall)
-      return launch_one<T, OutT, 1, UT, 4, 3, SPLIT>(x, w, bias, y, stats, a, s);
-  }
-  // bf16x3 linear layers / 1x1 convolutions with wide outputs: 256 x 256 tiles (64-byte K stages) when their rounds of
-  // 256 workgroups (one per CU) are filled well enough to beat 256 x 128 (profiles/r2d_bench_gemm.txt)
-  if constexpr (UT && SPLIT && sizeof(OutT) == 4) {
-    // (a 4-stage form of this pipeline -- three K tiles in flight -- measured the same: profiles/r3_rejected_experiments.txt)
-    if (use_wide_gemm(a.M, a.Cout, a.ks)) return launch_one<T, OutT, 4, UT, 4, 3, SPLIT, 64>(x, w, bias, y, stats, a, s);
-  }
-  // fp32 (MFMA-bound at 1/16 of the bf16 rate: a tile's time is its FLOPs, the operand stream is never the limit): pick
-  // the tile shape by whole-chip rounds.  The ResNet-C4 layers at 600x1200 have few tiles per CU (res4: 22 800 rows x
-  // 256 channels = 358 tiles of 128 x 128 on 256 CUs: two rounds for 1.4 rounds of work); 128 x 64 tiles pack the same
-  // layer into 716 / 768 slots (three per CU) -- cost = ceil(workgroups / 256) x tile area, smaller is better, ties to
-  // the larger tile.  SFOD_GEMM_FP32_TILES=0 restores the fixed rule (A/B).
-  if constexpr (sizeof(T) == 4 && UT) {
-    static const int cost_rule = []() { const char* e = getenv("SFOD_GEMM_FP32_TILES"); return e ? atoi(e) : 1; }();
-    if (cost_rule) {
-      auto rounds = [&](int bm, int bn) {
-        const int64_t wgs = (int64_t)((a.M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn);
-        return (double)((wgs + 255) / 256) * bm * bn;
-      };
-      const double c256 = rounds(256, 128) * 0.98, c128 = rounds(128, 128), c64 = rounds(128, 64) * 1.03;
-      if (c64 < c128 && c64 < c256) return launch_one<T, OutT, 1, UT, 2, 2, SPLIT>(x, w, bias, y, stats, a, s);
-      if (c256 <= c128) return launch_one<T, OutT, 2, UT, 4, 3, SPLIT>(x, w, bias, y, stats, a, s);
-      return launch_one<T, OutT, 2, UT, 2, 2, SPLIT>(x, w, bias, y, stats, a, s);
-    }
-  }
-  // 256 x 128 tiles with a 3-stage DMA pipeline once the grid still fills the chip (>= 2 tiles / CU)
-  const int64_t big_tiles = (int64_t)((a.M + 255) / 256) * ((a.Cout + 127) / 128);
-  if (UT && big_tiles >= 384) return launch_one<T, OutT, 2, UT, 4, 3, SPLIT>(x, w, bias, y, stats, a, s);
-  return launch_one<T, OutT, 2, UT, 2, 2, SPLIT>(x, w, bias, y, stats, a, s);
+#undef TILE
+  sfod_set_error("conv_fwd: tile shape %d is not built for these operands", (int)tile);
+  return SFOD_EBADARG;
 }
 
 template <typename T, typename OutT, int SPLIT = 0>
-static int launch_conv_fwd(const void* x, const void* w, const float* bias, void* y, float* stats,
+static int launch_conv_fwd(const ConvFwdPlan& p, const void* x, const void* w, const float* bias, void* y, float* stats,
                            const ConvArgs& a, hipStream_t s) {
-  const int cpt = a.Cin / Chunk<T>::E;
-  const bool ut = (a.ks == 1) || (cpt % 8 == 0);
-  if (ut) return launch_conv_fwd_ut<T, OutT, true, SPLIT>(x, w, bias, y, stats, a, s);
-  return launch_conv_fwd_ut<T, OutT, false, SPLIT>(x, w, bias, y, stats, a, s);
+  if (p.ut) return launch_tile<T, OutT, true, SPLIT>(p.tile, x, w, bias, y, stats, a, s);
+  return launch_tile<T, OutT, false, SPLIT>(p.tile, x, w, bias, y, stats, a, s);
 }
 
 extern "C" int sfod_conv_first_supported(int B, int H, int W, int Cin, int Cout, int dt, int ldy) {
   if (!(conv_shape_fits(B, H, W, Cin, Cout, 3) && sfod_ints_ok({ldy}))) return 0;      // hostile extents: not served / nothing
-  return use_first_kernel(B, H, W, Cin, Cout, 3, dt, ldy, sfod_is_pairs(dt) ? SFOD_F32 : SFOD_BF16) ? 1 : 0;
+  return conv_fwd_plan(B, H, W, Cin, Cout, 3, dt, sfod_is_pairs(dt) ? SFOD_F32 : dt, ldy, true, 0).kind == CONV_FIRST ? 1 : 0;
 }
 
 extern "C" int sfod_conv_first_fused(const void* x, const void* w, const float* bias, const float* scale,
@@ -763,37 +794,6 @@ extern "C" int sfod_conv_first_fused_ws(const void* x, const void* w, const uint
 
 extern "C" int sfod_conv_fwd_scratch(const void* x, const void* w, const uint32_t* w_absmax, const float* bias, void* y,
                                      int B, int H, int W, int Cin, int Cout, int ksize, int ldy, int act, float* stats,
-                                     int dt, int out_dt, void* scratch, int64_t scratch_bytes, void* stream);
-
-extern "C" int sfod_conv_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W,
-                             int Cin, int Cout, int ksize, int ldy, int act, float* stats, int dt,
-                             int out_dt, void* stream) {
-  SFOD_REQUIRE_EXTENTS("conv_fwd", B, H, W, Cin, Cout, ksize, ldy);
-  return sfod_conv_fwd_ws(x, w, nullptr, bias, y, B, H, W, Cin, Cout, ksize, ldy, act, stats, dt, out_dt, stream);
-}
-
-extern "C" int sfod_conv_fwd_ws(const void* x, const void* w, const uint32_t* w_absmax, const float* bias, void* y, int B,
-                                int H, int W, int Cin, int Cout, int ksize, int ldy, int act, float* stats, int dt,
-                                int out_dt, void* stream) {
-  SFOD_REQUIRE_EXTENTS("conv_fwd_ws", B, H, W, Cin, Cout, ksize, ldy);
-  return sfod_conv_fwd_scratch(x, w, w_absmax, bias, y, B, H, W, Cin, Cout, ksize, ldy, act, stats, dt, out_dt, nullptr, 0,
-                               stream);
-}
-
-// Scratch the caller may offer to sfod_conv_fwd_scratch for this shape (0: none wanted): today the slabs of the split-K form
-// of linear layers with few rows (splitk_plan above).
-extern "C" int64_t sfod_conv_fwd_scratch_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int dt, int out_dt,
-                                               int with_stats) {
-  if (!conv_shape_fits(B, H, W, Cin, Cout, ksize)) return 0;      // hostile extents: not served / nothing
-  if (dt != SFOD_F32 && dt != SFOD_BF16 && !sfod_is_pairs(dt)) return 0;
-  const int E = (dt == SFOD_F32) ? 4 : 8;
-  if (ksize != 1 || Cout % 4 != 0 || Cin % E != 0 || (int64_t)B * H * W == 0 || (int64_t)B * H * W > (1 << 24)) return 0;
-  const int S = splitk_plan(B * H * W, phys_ch(dt, Cin) / E, Cout, ksize, out_dt == SFOD_F32, with_stats != 0);
-  return (int64_t)S * B * H * W * Cout * 4;
-}
-
-extern "C" int sfod_conv_fwd_scratch(const void* x, const void* w, const uint32_t* w_absmax, const float* bias, void* y,
-                                     int B, int H, int W, int Cin, int Cout, int ksize, int ldy, int act, float* stats,
                                      int dt, int out_dt, void* scratch, int64_t scratch_bytes, void* stream) {
   sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE(conv_shape_fits(B, H, W, Cin, Cout, ksize) && sfod_ints_ok({ldy}) && sfod_i64s_ok({scratch_bytes}),
@@ -809,16 +809,25 @@ extern "C" int sfod_conv_fwd_scratch(const void* x, const void* w, const uint32_
   SFOD_REQUIRE(Cin % E == 0, "conv: Cin must be a multiple of the 16-byte chunk (operand pairs: of 8)");
   SFOD_REQUIRE(!sfod_is_pairs(dt) || out_dt == SFOD_F32, "conv: operand pairs write fp32");
   if ((int64_t)B * H * W == 0) return 0;
+  SFOD_REQUIRE(dt != SFOD_F32 || out_dt == SFOD_F32, "conv: fp32 compute writes fp32");
+  const ConvFwdPlan p = conv_fwd_plan(B, H, W, Cin, Cout, ksize, dt, out_dt, ldy, stats != nullptr,
+                                      scratch != nullptr ? scratch_bytes : 0);
+  SFOD_REQUIRE(p.kind != CONV_NONE, "conv_fwd: negative or oversized extent");
+  // (a launch with the query's own assumptions is the query's plan: nothing to ask again)
+  const bool as_query = ldy == Cout && out_dt == (sfod_is_pairs(dt) ? SFOD_F32 : dt);
+  SFOD_REQUIRE(stats == nullptr || as_query || p.stats_blocks == sfod_conv_stats_blocks(B, H, W, Cin, Cout, ksize, dt),
+               "conv_fwd: with this ldy / out_dt the launch writes another number of statistics blocks than "
+               "sfod_conv_stats_blocks answers (it assumes dense rows and the operands' own output type)");
   hipStream_t s = (hipStream_t)stream;
-  if (use_first_kernel(B, H, W, Cin, Cout, ksize, dt, ldy, out_dt))
-    return sfod_f1_launch(x, w, bias, y, stats, B, H, W, ldy, act, s, nullptr, nullptr, split_code(dt), w_absmax);
   const int split = split_code(dt);
   Cin = phys_ch(dt, Cin);           // from here on: bf16 channels as stored
-  if (ksize == 3 && is_bf16_storage(dt)) {
-    const P3Plan p = sfod_p3_plan(B, H, W, Cin, Cout, split != 0);
-    if (use_patch_kernel(p, B, H, W, ksize, dt))
-      return sfod_p3_launch(p, x, w, bias, y, stats, B, H, W, Cin, Cout, ldy, act, out_dt == SFOD_F32, s, split, nullptr,
+  switch (p.kind) {
+    case CONV_FIRST:
+      return sfod_f1_launch(x, w, bias, y, stats, B, H, W, ldy, act, s, nullptr, nullptr, split, w_absmax);
+    case CONV_PATCH:
+      return sfod_p3_launch(p.p3, x, w, bias, y, stats, B, H, W, Cin, Cout, ldy, act, out_dt == SFOD_F32, s, split, nullptr,
                             w_absmax);
+    default: break;
   }
   ConvArgs a;
   a.wamax = w_absmax;
@@ -831,79 +840,67 @@ extern "C" int sfod_conv_fwd_scratch(const void* x, const void* w, const uint32_
   }
   a.kchunks = ksize * ksize * cpt;
   a.kt_per = 0; a.nsplit = 1; a.slab = 0;
-  if (scratch != nullptr && Cout % 4 == 0 && (int64_t)a.M <= (1 << 24)) {
-    const int S = splitk_plan(a.M, a.kchunks, Cout, ksize, out_dt == SFOD_F32, stats != nullptr);
-    if (S >= 2 && scratch_bytes >= (int64_t)S * a.M * Cout * 4) {
-      float* ws = (float*)scratch;
-      if (dt == SFOD_F32) return launch_splitk<float, 0>(x, w, bias, (float*)y, a, S, ws, s);
-      if (split == 2) return launch_splitk<bf16_t, 2>(x, w, bias, (float*)y, a, S, ws, s);
-      if (split) return launch_splitk<bf16_t, 1>(x, w, bias, (float*)y, a, S, ws, s);
-      return launch_splitk<bf16_t, 0>(x, w, bias, (float*)y, a, S, ws, s);
-    }
+  if (p.kind == CONV_GEMM_SPLITK) {
+    float* ws = (float*)scratch;
+    if (dt == SFOD_F32) return launch_splitk<float, 0>(x, w, bias, (float*)y, a, p.splitk, ws, s);
+    if (split == 2) return launch_splitk<bf16_t, 2>(x, w, bias, (float*)y, a, p.splitk, ws, s);
+    if (split) return launch_splitk<bf16_t, 1>(x, w, bias, (float*)y, a, p.splitk, ws, s);
+    return launch_splitk<bf16_t, 0>(x, w, bias, (float*)y, a, p.splitk, ws, s);
   }
-  if (dt == SFOD_F32) {
-    SFOD_REQUIRE(out_dt == SFOD_F32, "conv: fp32 compute writes fp32");
-    return launch_conv_fwd<float, float>(x, w, bias, y, stats, a, s);
-  }
-  if (split == 2) return launch_conv_fwd<bf16_t, float, 2>(x, w, bias, y, stats, a, s);
-  if (split) return launch_conv_fwd<bf16_t, float, 1>(x, w, bias, y, stats, a, s);
-  if (out_dt == SFOD_F32) return launch_conv_fwd<bf16_t, float>(x, w, bias, y, stats, a, s);
-  return launch_conv_fwd<bf16_t, bf16_t>(x, w, bias, y, stats, a, s);
+  if (dt == SFOD_F32) return launch_conv_fwd<float, float>(p, x, w, bias, y, stats, a, s);
+  if (split == 2) return launch_conv_fwd<bf16_t, float, 2>(p, x, w, bias, y, stats, a, s);
+  if (split) return launch_conv_fwd<bf16_t, float, 1>(p, x, w, bias, y, stats, a, s);
+  if (out_dt == SFOD_F32) return launch_conv_fwd<bf16_t, float>(p, x, w, bias, y, stats, a, s);
+  return launch_conv_fwd<bf16_t, bf16_t>(p, x, w, bias, y, stats, a, s);
+}
+
+extern "C" int sfod_conv_fwd_ws(const void* x, const void* w, const uint32_t* w_absmax, const float* bias, void* y, int B,
+                                int H, int W, int Cin, int Cout, int ksize, int ldy, int act, float* stats, int dt,
+                                int out_dt, void* stream) {
+  SFOD_REQUIRE_EXTENTS("conv_fwd_ws", B, H, W, Cin, Cout, ksize, ldy);
+  return sfod_conv_fwd_scratch(x, w, w_absmax, bias, y, B, H, W, Cin, Cout, ksize, ldy, act, stats, dt, out_dt, nullptr, 0,
+                               stream);
+}
+
+extern "C" int sfod_conv_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W,
+                             int Cin, int Cout, int ksize, int ldy, int act, float* stats, int dt,
+                             int out_dt, void* stream) {
+  SFOD_REQUIRE_EXTENTS("conv_fwd", B, H, W, Cin, Cout, ksize, ldy);
+  return sfod_conv_fwd_ws(x, w, nullptr, bias, y, B, H, W, Cin, Cout, ksize, ldy, act, stats, dt, out_dt, stream);
 }
 
 // 3x3 convolution whose INPUT is the previous layer's pre-BatchNorm output: relu(bn(x)) and the operand-pair split happen in
 // the kernel's LDS patch instead of in a separate elementwise pass (forward-only passes: nobody else needs the activated
-// tensor).  _supported: 1 when the shape is served (SFOD_BF16X3 operands, the 256 x 128 halo-patch shape, Cin % 32 == 0).
-extern "C" int sfod_conv_fwd_bnin_supported(int B, int H, int W, int Cin, int Cout, int dt) {
-  if (!conv_shape_fits(B, H, W, Cin, Cout, 3)) return 0;      // hostile extents: not served / nothing
-  if (dt != SFOD_BF16X3 || (int64_t)B * H * W == 0 || g_conv_algo == 1) return 0;
-  const int pc = phys_ch(dt, Cin);
-  const P3Plan p = sfod_p3_plan(B, H, W, pc, Cout, 1);
-  return (use_patch_kernel(p, B, H, W, 3, dt) && sfod_p3_bnin_ok(p, pc, 1)) ? 1 : 0;
-}
-
+// tensor).
 extern "C" int sfod_conv_fwd_bnin(const float* x_pre, const float* in_mean, const float* in_invstd, const float* in_gamma,
                                   const float* in_beta, const void* w, const float* bias, float* y, int B, int H, int W,
                                   int Cin, int Cout, int ldy, int act, float* stats, int dt, void* stream) {
   sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE(conv_shape_fits(B, H, W, Cin, Cout, 3) && sfod_ints_ok({ldy}), "conv_fwd_bnin: negative or oversized extent");
-  SFOD_REQUIRE(sfod_conv_fwd_bnin_supported(B, H, W, Cin, Cout, dt), "conv_fwd_bnin: shape not served (sfod_conv_fwd_bnin_supported)");
+  const ConvFwdPlan p = conv_fwd_plan(B, H, W, Cin, Cout, 3, dt, SFOD_F32, ldy, stats != nullptr, 0);
+  SFOD_REQUIRE(p.bnin_ok, "conv_fwd_bnin: shape not served (sfod_conv_fwd_bnin_supported)");
   SFOD_REQUIRE(x_pre && in_mean && in_invstd && in_gamma && in_beta && w && y, "conv_fwd_bnin: null argument");
   SFOD_REQUIRE(ldy >= Cout, "conv_fwd_bnin: ldy < Cout");
-  const int pc = phys_ch(dt, Cin);
-  const P3Plan p = sfod_p3_plan(B, H, W, pc, Cout, 1);
   const P3BnIn bnin{in_mean, in_invstd, in_gamma, in_beta};
-  return sfod_p3_launch(p, x_pre, w, bias, y, stats, B, H, W, pc, Cout, ldy, act, 1, (hipStream_t)stream, 1, nullptr, nullptr,
-                        &bnin);
+  return sfod_p3_launch(p.p3, x_pre, w, bias, y, stats, B, H, W, phys_ch(dt, Cin), Cout, ldy, act, 1, (hipStream_t)stream, 1,
+                        nullptr, nullptr, &bnin);
 }
 
 // Data gradient of a 3x3 convolution (x = dy of the layer above as operand, w = its rotated weights) whose epilogue also
 // makes the BatchNorm-backward partial sums of the layer BELOW, i.e. of the tensor this launch writes (dz): halo-patch
-// kernel with fp32 output only.  sfod_conv_dgrad_bnred_blocks: number of partial rows it writes (0: shape / dtype not
-// served -- run sfod_conv_fwd and the separate reduction instead).
-extern "C" int sfod_conv_dgrad_bnred_blocks(int B, int H, int W, int Cin, int Cout, int dt) {
-  if (!conv_shape_fits(B, H, W, Cin, Cout, 3)) return 0;      // hostile extents: not served / nothing
-  if (dt != SFOD_BF16X3 && dt != SFOD_BF16) return 0;
-  if (dt == SFOD_BF16) return 0;        // bf16 mode writes bf16 gradients: no fp32 tile to reduce
-  if (Cout % 4 != 0) return 0;
-  const P3Plan p = sfod_p3_plan(B, H, W, phys_ch(dt, Cin), Cout, sfod_is_pairs(dt));
-  return use_patch_kernel(p, B, H, W, 3, dt) ? p.nblk : 0;
-}
-
+// kernel with fp32 output only.
 extern "C" int sfod_conv_dgrad_bnred(const void* x, const void* w, void* dz, int B, int H, int W, int Cin, int Cout,
                                      int dt, const float* y, const float* mean, const float* invstd,
                                      const float* gamma, const float* beta, float* red_ws, void* stream) {
   sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
   SFOD_REQUIRE(conv_shape_fits(B, H, W, Cin, Cout, 3), "conv_dgrad_bnred: negative or oversized extent");
   SFOD_REQUIRE(x != nullptr && w != nullptr && dz != nullptr, "conv_dgrad_bnred: null operand");
-  SFOD_REQUIRE(sfod_conv_dgrad_bnred_blocks(B, H, W, Cin, Cout, dt) > 0,
-               "conv_dgrad_bnred: shape not served (sfod_conv_dgrad_bnred_blocks)");
+  const ConvFwdPlan p = conv_fwd_plan(B, H, W, Cin, Cout, 3, dt, SFOD_F32, Cout, false, 0);
+  SFOD_REQUIRE(p.bnred_blocks > 0, "conv_dgrad_bnred: shape not served (sfod_conv_dgrad_bnred_blocks)");
   SFOD_REQUIRE(y && mean && invstd && gamma && beta && red_ws, "conv_dgrad_bnred: null argument");
-  const int pc = phys_ch(dt, Cin);
-  const P3Plan p = sfod_p3_plan(B, H, W, pc, Cout, sfod_is_pairs(dt));
   const P3BnRed red{y, mean, invstd, gamma, beta, red_ws};
-  return sfod_p3_launch(p, x, w, nullptr, dz, nullptr, B, H, W, pc, Cout, Cout, 0, 1, (hipStream_t)stream,
-                        dt == SFOD_BF16X3, &red);
+  return sfod_p3_launch(p.p3, x, w, nullptr, dz, nullptr, B, H, W, phys_ch(dt, Cin), Cout, Cout, 0, 1, (hipStream_t)stream, 1,
+                        &red);
 }
 
 // =============================================================================================
@@ -1404,21 +1401,9 @@ static int w3_launch_chunked(const void* x, const void* dy, float* dw, void* ws,
 // linear, first layer, fp32) combine theirs with float atomics, whose arrival order differs from run to run.  In this mode
 // they store each split's partial tile into a slab of the workspace instead and k_wgrad_slab_sum adds the slabs in split
 // order: run-to-run bit-identical gradients (tests/test_gpu_trajectory.py), for one more pass over splits x |dw| floats.
-static std::atomic<int> g_deterministic{-1};
-extern "C" int sfod_set_deterministic(int on) {
-  g_deterministic.store(on ? 1 : 0, std::memory_order_relaxed);
-  return 0;
-}
-bool sfod_deterministic() {
-  int v = g_deterministic.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* ev = getenv("SFOD_DETERMINISTIC");
-    int want = (ev && atoi(ev) != 0) ? 1 : 0, expect = -1;
-    g_deterministic.compare_exchange_strong(expect, want, std::memory_order_relaxed);
-    v = g_deterministic.load(std::memory_order_relaxed);
-  }
-  return v != 0;
-}
+static SfodKnob g_deterministic{"SFOD_DETERMINISTIC", 0, sfod_knob_bool};
+extern "C" int sfod_set_deterministic(int on) { g_deterministic.set(on); return 0; }
+bool sfod_deterministic() { return g_deterministic.get() != 0; }
 extern "C" int sfod_get_deterministic(void) { return sfod_deterministic() ? 1 : 0; }
 
 __global__ void __launch_bounds__(256) k_wgrad_slab_sum(const float* __restrict__ ws, float* __restrict__ dw, int64_t n,

@@ -607,7 +607,7 @@ k_roi_align_bwd_tiled(const T* __restrict__ dout, int H, int W, int C, const flo
 }
 
 // SFOD_ROI_BWD_ATOMIC=1 selects the scatter (atomic) form for A/B measurements (pooled <= 8: its register tile).
-static const bool g_roi_bwd_tiled = []() { const char* e = getenv("SFOD_ROI_BWD_ATOMIC"); return !(e && e[0] == '1'); }();
+static const bool g_roi_bwd_tiled = sfod_env_int("SFOD_ROI_BWD_ATOMIC", 0) != 1;
 
 template <typename T>
 static int dispatch_roi_bwd(const void* dout, int B, int H, int W, int C, const float* rois, int R, int pooled,
@@ -649,12 +649,12 @@ extern "C" int sfod_roi_align_fwd_opt(const void* feat, int B, int H, int W, int
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)pooled * (H + W) * 4 + 4 * pooled * 4;
   // SFOD_ROI_FWD_SEP14=0: the sample-by-sample kernel at 14 (A/B)
-  static const bool sep14 = []() { const char* e = getenv("SFOD_ROI_FWD_SEP14"); return !(e && e[0] == '0'); }();
+  static const bool sep14 = sfod_env_int("SFOD_ROI_FWD_SEP14", 1) != 0;
   if ((pooled == 7 || (pooled == 14 && sep14)) && lds <= 48 * 1024) {       // the configs' POOLER_RESOLUTION and d2's default: separable form
     // channel blocks (one L2-resident slice of the feature map at a time); SFOD_ROI_CBLK: logical channels per block
     // (A/B; 0: one workgroup per box), SFOD_ROI_NT=1: non-temporal output stores
-    static const int cblk_env = []() { const char* e = getenv("SFOD_ROI_CBLK"); return e ? atoi(e) : ROI_CBLK_DEFAULT; }();
-    static const int nt = []() { const char* e = getenv("SFOD_ROI_NT"); return e ? atoi(e) : ROI_NT_DEFAULT; }();
+    static const int cblk_env = sfod_env_int("SFOD_ROI_CBLK", ROI_CBLK_DEFAULT);
+    static const int nt = sfod_env_int("SFOD_ROI_NT", ROI_NT_DEFAULT);
     const int V = (dt == SFOD_F32) ? 4 : 8;
     int ncb = 1;
     if (cblk_env > 0 && cblk_env % V == 0 && C % cblk_env == 0 && C > cblk_env) ncb = C / cblk_env;

@@ -24,7 +24,6 @@
 //         ahead behind counted s_waitcnt vmcnt(N).
 #include "conv_internal.h"
 #include <type_traits>
-#include <atomic>
 #include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -923,23 +922,9 @@ k_wgrad_reduce(const float* __restrict__ slab, float* __restrict__ dw, int64_t n
 // A/B knob of the bf16x3 weight gradient (environment SFOD_W3_PIPE): 2 (default) the 64 x 64-block kernel on 128-pixel
 // tiles where Cin >= 64 (else 1), 1 the pipelined 64 x 32-block loop, 0 the round-2 loop.  1 and 0 give bit-identical
 // results; 2 sums the same products in a different grouping (other pixel tiles).
-static std::atomic<int> g_w3_pipe{-1};   // -1: not initialised (SFOD_W3_PIPE or 2)
-extern "C" int sfod_set_wgrad3x3_pipe(int on) {
-  g_w3_pipe.store((on < 0 || on > 2) ? 2 : on, std::memory_order_relaxed);
-  return 0;
-}
-static int w3_mode() {
-  int m = g_w3_pipe.load(std::memory_order_relaxed);
-  if (m < 0) {
-    const char* ev = getenv("SFOD_W3_PIPE");
-    m = ev ? atoi(ev) : 2;
-    if (m < 0 || m > 2) m = 2;
-    int expect = -1;
-    g_w3_pipe.compare_exchange_strong(expect, m, std::memory_order_relaxed);
-    m = g_w3_pipe.load(std::memory_order_relaxed);
-  }
-  return m;
-}
+static SfodKnob g_w3_pipe{"SFOD_W3_PIPE", 2, [](int on) { return (on < 0 || on > 2) ? 2 : on; }};
+extern "C" int sfod_set_wgrad3x3_pipe(int on) { g_w3_pipe.set(on); return 0; }
+static int w3_mode() { return g_w3_pipe.get(); }
 
 // split != 0: SFOD_BF16X3 operands; Cin / Cout / lddy are LOGICAL channel counts in either case
 W3Plan sfod_w3_plan(int B, int H, int W, int Cin, int Cout, int lddy, int split) {

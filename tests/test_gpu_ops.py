@@ -362,6 +362,32 @@ def test_one_launch_batchnorm_finalize_is_the_two_launch_one_bit_for_bit(native,
         assert stats.nblk <= 64, stats.nblk
 
 
+def test_bn_finalize_fused_setter_is_read_back_through_the_workspace(native):
+    """sfod_set_bn_finalize_fused: 0 off, every other value on.  No query depends on the knob, but the one-launch form never
+    touches the workspace and the two-launch form writes its partial sums there: which form ran is read off a NaN-filled
+    workspace, on a layer of <= 64 statistics blocks (where the knob decides)."""
+    B, H, W, C = 1, 9, 11, 64
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(B, H, W, 64, generator=g).to(DEV)
+    wp = native.pack_conv_weight(torch.randn(C, 64, 1, 1, generator=g).to(DEV) * 0.2, 64, native.F32)
+    _, stats = native.conv_fwd(x, wp, None, C, 1, want_stats=True)
+    assert stats.nblk <= 64
+
+    def two_launches(value):
+        native.load().sfod_set_bn_finalize_fused(value)
+        ws = torch.full((native.query("sfod_bn_finalize_ws_floats", C),), float("nan"), dtype=torch.float32, device=DEV)
+        mean, invstd, rm, rv = (torch.zeros(C, device=DEV) for _ in range(4))
+        native.call("sfod_bn_finalize", stats, stats.nblk, B * H * W, C, mean, invstd, rm, rv, 0.1, 1e-5, 0, None, ws)
+        torch.cuda.synchronize()
+        assert torch.isfinite(mean).all() and (invstd > 0).all()
+        return not bool(torch.isnan(ws).all())
+
+    try:
+        assert [two_launches(v) for v in (0, 1, 0, 5, 0, -1, 0, 1 << 20)] == [True, False] * 4
+    finally:
+        native.set_bn_finalize_fused(True)
+
+
 # -------------------------------------------------------------------------------------------------
 # BatchNorm + ReLU + pool
 # -------------------------------------------------------------------------------------------------
