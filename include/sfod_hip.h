@@ -224,6 +224,25 @@ int sfod_conv_wgrad_oihw_supported(int B, int H, int W, int Cin, int Cout, int k
 int sfod_conv_wgrad_oihw(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin,
                          int Cout, int ksize, int lddy, int dt, int accumulate, void* ws,
                          int64_t ws_bytes, void* stream);
+/* First VGG layer (conv1_1: x operand pairs with Cin = one 8-channel group, Cout = 64, no data gradient): the weight gradient
+ * straight from the INPUTS of its BatchNorm + ReLU backward.  dz (gradient of the activated output) and y (saved
+ * pre-BatchNorm output) are fp32 [B,H,W,64]; dgamma / dbeta are the FINALIZED sums of this layer (sfod_bn_relu_pool_bwd with
+ * dy = NULL produces them without the apply pass).  The kernel (k_first_wgrad_bn) forms every dy pair in registers with the
+ * expression and the (hi, lo) split of sfod_bn_relu_pool_bwd's apply pass and sums the products in the order of
+ * sfod_conv_wgrad's / sfod_conv_wgrad_oihw's kernel: dw is BIT-IDENTICAL to sfod_bn_relu_pool_bwd(dy as SFOD_BF16X3)
+ * followed by sfod_conv_wgrad (oihw = 0: dw packed [64][9][8], added into; `accumulate` ignored) or sfod_conv_wgrad_oihw
+ * (oihw = 1: dw [64][8][3][3], overwritten or, accumulate = 1, added into), and dy (4 bytes x B*H*W*64, written and read
+ * back once) never exists.  ws: sfod_conv_wgrad_ws_bytes of (B, H, W, 8, 64, 3, 64, SFOD_BF16X3).
+ * _supported: 1 only for Cin = 8, Cout = 64, pool = 0 (no pooling, ReLU: the `pool` flags of sfod_bn_relu_pool_bwd), dt =
+ * SFOD_BF16X3 (x), y_dt = SFOD_F32, a shape sfod_conv_wgrad_oihw serves with its halo-patch kernel in ONE sub-batch (tensors
+ * below 2 GiB), and the knob below at 1; elsewhere the caller runs the two launches.
+ * sfod_set_first_wgrad_fused (environment SFOD_FIRST_WGRAD_FUSED, default 1): A/B knob, 0 = the query refuses. */
+int sfod_conv_first_wgrad_bn_supported(int B, int H, int W, int Cin, int Cout, int pool, int dt, int y_dt);
+int sfod_conv_first_wgrad_bn(const void* x, const void* dz, const void* y, const float* mean, const float* invstd,
+                             const float* gamma, const float* beta, const float* dgamma, const float* dbeta,
+                             float* dw, int B, int H, int W, int Cin, int Cout, int dt, int oihw, int accumulate,
+                             void* ws, int64_t ws_bytes, void* stream);
+int sfod_set_first_wgrad_fused(int on);
 
 /* weight (re)packing between the reference's state-dict layouts and the kernel layouts.
  * OIHW fp32 [Cout][Cin][KH][KW] -> packed [Cout][KH*KW][CinPad] (dt); rot180=1 additionally
@@ -322,7 +341,9 @@ int sfod_bn_add_relu_fwd(const void* y, const float* mean, const float* invstd, 
  * xhat = (y - mean) * invstd and M = B * H * W: the leftover pixels of an odd H / W count in M, their g is 0 and their dy is
  * the mean terms alone.  A pooled map without any window (H or W = 1) has an empty dz (may be NULL): dgamma = dbeta = 0.
  * dgamma_acc / dbeta_acc (may be NULL): the parameters' gradient accumulators (+= this call's dgamma /
- * dbeta), so the caller needs no separate accumulate pass per BatchNorm layer. */
+ * dbeta), so the caller needs no separate accumulate pass per BatchNorm layer.
+ * dy == NULL: the sums only (reduction, or the pre-reduced rows, then the same finalize) -- no apply pass; for a layer
+ * whose dy is formed by its consumer (sfod_conv_first_wgrad_bn). */
 int sfod_bn_relu_pool_bwd(const void* dz, const void* y, const float* mean, const float* invstd,
                           const float* gamma, const float* beta, void* dy, float* dgamma,
                           float* dbeta, float* dgamma_acc, float* dbeta_acc, float* ws, int B, int H,

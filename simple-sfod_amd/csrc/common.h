@@ -209,6 +209,34 @@ template <typename T> __device__ __forceinline__ float get_elem(const T* base, i
 template <> __device__ __forceinline__ float get_elem<split_t>(const split_t* base, int64_t idx) { return split_get(base, idx); }
 template <> __device__ __forceinline__ float get_elem<splith_t>(const splith_t* base, int64_t idx) { return split_get(base, idx); }
 
+// BatchNorm (+ ReLU) backward of ONE element without pooling: v the saved pre-BatchNorm output, gz the gradient of the
+// activated output; per channel sc = invstd * gamma, sh = beta, k1 = dbeta * invM, k2 = dgamma * invM (both ROUNDED
+// products, computed once per channel), invM = 1 / M.  dy = sc * bn_bwd_unscaled(...).  k_bn_bwd_apply and the first
+// layer's fused weight gradient (k_first_wgrad_bn) both go through THESE functions, so that their dy agree bit for bit.
+// The roundings are spelled out: left to the compiler, the contraction of the inlined expression depends on what
+// surrounds it.  They are the ones the compiler has always generated for k_bn_bwd_apply's flat walk: two fused
+// multiply-adds (the pre-activation and the xhat term) around a plain g - k1, a rounded product sc * r for the value --
+// and, where dy is written as a bf16 pair, the residual of the UNROUNDED product: lo = bf16(fma(sc, r, -hi)), not
+// bf16(round(sc * r) - hi) (bn_bwd_pair).
+template <int RELU>
+__device__ __forceinline__ float bn_bwd_unscaled(float v, float gz, float mu, float invs, float sc, float sh, float k1, float k2) {
+#pragma clang fp contract(off)
+  const float d = v - mu;
+  const float xh = d * invs;
+  const float zp = __builtin_fmaf(d, sc, sh);
+  const float g = (!RELU || zp > 0.f) ? gz : 0.f;
+  return __builtin_fmaf(-xh, k2, g - k1);
+}
+__device__ __forceinline__ float bn_bwd_value(float sc, float r) {
+#pragma clang fp contract(off)
+  return sc * r;
+}
+__device__ __forceinline__ void bn_bwd_pair(float sc, float r, bf16_t& h, bf16_t& l) {
+#pragma clang fp contract(off)
+  h = (bf16_t)(sc * r);
+  l = (bf16_t)__builtin_fmaf(sc, r, -(float)h);
+}
+
 // the split-precision product's MFMA on either pair format (FMT: 1 = bf16 pairs, 2 = f16 pairs; same registers, same rate)
 typedef __attribute__((ext_vector_type(8))) __bf16 sfod_bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 sfod_f16x8;

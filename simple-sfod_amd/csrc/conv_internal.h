@@ -58,6 +58,24 @@ W3Plan sfod_w3_plan(int B, int H, int W, int Cin, int Cout, int lddy, int split 
 int sfod_w3_launch(const W3Plan& p, const void* x, const void* dy, float* dw, void* ws, int B, int H, int W,
                    int Cin, int Cout, int lddy, int out_mode, hipStream_t s, int split = 0);
 
+// First layer (Cin = 8, Cout = lddy = 64, bf16 pairs, no data gradient): the same slabs from the INPUTS of the BatchNorm
+// backward apply pass -- k_first_wgrad_bn forms each dy pair in registers (bn_bwd_unscaled + bn_bwd_pair of common.h) and walks
+// the tiles, chunks and k-step groups of plan `p` exactly like k_wgrad3x3_patch<4, true, .>: dw is bit-identical to
+// sfod_bn_relu_pool_bwd (no pooling, ReLU, dy as pairs) followed by sfod_w3_launch, and dy never exists in memory.
+struct W3BnApply {
+  const float* dz;       // [B,H,W,64] gradient of the activated output
+  const float* y;        // [B,H,W,64] saved pre-BatchNorm output
+  const float* mean;
+  const float* invstd;
+  const float* gamma;
+  const float* beta;
+  const float* dgamma;   // finalized sums of this layer's BatchNorm backward
+  const float* dbeta;
+};
+bool sfod_w3_bn_ok(const W3Plan& p, int Cin, int Cout);
+int sfod_w3_bn_launch(const W3Plan& p, const void* x, const W3BnApply& bn, float* dw, void* ws, int B, int H, int W,
+                      int out_mode, hipStream_t s);
+
 // ---- deterministic mode (gemm_conv.hip: sfod_set_deterministic / SFOD_DETERMINISTIC) -----------------------------------
 bool sfod_deterministic();
 

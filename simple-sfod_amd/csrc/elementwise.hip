@@ -1111,13 +1111,18 @@ k_bn_bwd_apply(const T* __restrict__ dz, const T* __restrict__ y, const float* _
         load_n<T, V>(y + t * V, v);
         load_n<T, V>(dz + t * V, gz);
 #pragma unroll
-        for (int i = 0; i < V; ++i) {
-          const float xh = (v[i] - mu[i]) * invs[i];
-          const float zp = (v[i] - mu[i]) * sc[i] + sh[i];
-          const float g = (!RELU || zp > 0.f) ? gz[i] : 0.f;
-          o[i] = sc[i] * (g - k1[i] - xh * k2[i]);
+        for (int i = 0; i < V; ++i) o[i] = bn_bwd_unscaled<RELU>(v[i], gz[i], mu[i], invs[i], sc[i], sh[i], k1[i], k2[i]);
+        if constexpr (std::is_same<TO, split_t>::value) {      // V = 8: one (8 hi | 8 lo) group
+          union { bf16_t h[8]; uint4 q; } hi, lo;
+#pragma unroll
+          for (int i = 0; i < V; ++i) bn_bwd_pair(sc[i], o[i], hi.h[i], lo.h[i]);
+          store16<false>(dy + t * V, hi.q);
+          store16<false>(reinterpret_cast<uint4*>(dy + t * V) + 1, lo.q);
+        } else {
+#pragma unroll
+          for (int i = 0; i < V; ++i) o[i] = bn_bwd_value(sc[i], o[i]);
+          store_n<TO, V>(dy + t * V, o);
         }
-        store_n<TO, V>(dy + t * V, o);
       }
       return;
     }
@@ -1233,8 +1238,9 @@ extern "C" int sfod_bn_relu_pool_bwd(const void* dz, const void* y, const float*
     } else                                                                                             \
       hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(cdiv(2 * C, 64)), dim3(1024), 0, s, ws,               \
                          reduced_blocks ? reduced_blocks : grid1, C, dgamma, dbeta, dgamma_acc, dbeta_acc); \
-    hipLaunchKernelGGL((k_bn_bwd_apply<T, P, R, TO>), dim3(grid3), dim3(256), 0, s, (const T*)dz,      \
-                       (const T*)y, mean, invstd, gamma, beta, dgamma, dbeta, (TO*)dy, B, H, W, C);    \
+    if (dy != nullptr)                                                                                 \
+      hipLaunchKernelGGL((k_bn_bwd_apply<T, P, R, TO>), dim3(grid3), dim3(256), 0, s, (const T*)dz,    \
+                         (const T*)y, mean, invstd, gamma, beta, dgamma, dbeta, (TO*)dy, B, H, W, C);  \
   } while (0)
 #define LAUNCH4(T, TO)                                                           \
   do {                                                                           \
@@ -1248,7 +1254,7 @@ extern "C" int sfod_bn_relu_pool_bwd(const void* dz, const void* y, const float*
 #undef LAUNCH
   int rc = sfod_check_launch("bn_relu_pool_bwd");
   if (rc) return rc;
-  if (pool && ((H & 1) || (W & 1))) {
+  if (dy != nullptr && pool && ((H & 1) || (W & 1))) {
     const int L = 2 * Ho * (W - 2 * Wo) + (H - 2 * Ho) * W;
     const int grid = ew_grid((int64_t)B * L * (C / VO));
     if (dy_dt == SFOD_BF16X3)

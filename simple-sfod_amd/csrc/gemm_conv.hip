@@ -590,7 +590,8 @@ static ConvFwdPlan conv_fwd_plan(int B, int H, int W, int Cin, int Cout, int ksi
   const bool pairs = sfod_is_pairs(dt);
   // hostile extents (pairs: the physical channel count is an int as well): not served / nothing
   if (!conv_shape_fits(B, H, W, Cin, Cout, ksize) || !sfod_prod_fits({Cin, pairs ? 2 : 1})) return p;
-  const int M = B * H * W, pc = phys_ch(dt, Cin), algo = g_conv_algo;
+  // (an empty tensor passes conv_shape_fits whatever its other extents are: B * H may not fit an int on the way to 0)
+  const int M = (int)((int64_t)B * H * W), pc = phys_ch(dt, Cin), algo = g_conv_algo;
   // first VGG layer: 3 real channels in one 8-wide chunk, 64 outputs; bf16 in / bf16 out, or operand pairs in / fp32 out
   const bool first_types = (dt == SFOD_BF16 && out_dt == SFOD_BF16) || (pairs && out_dt == SFOD_F32);
   if (ksize == 3 && first_types && Cin == 8 && Cout == 64 && ldy % 8 == 0 && algo != 1 && M >= 4096) {
@@ -1507,6 +1508,50 @@ extern "C" int sfod_conv_wgrad_oihw(const void* x, const void* dy, float* dw_oih
   SFOD_REQUIRE(nb > 0, "wgrad_oihw: shape not served by the halo-patch kernel (query sfod_conv_wgrad_oihw_supported)");
   return w3_launch_chunked(x, dy, dw_oihw, ws, ws_bytes, B, H, W, Cin, Cout, lddy, dt, accumulate ? 2 : 1, nb,
                            (hipStream_t)stream);
+}
+
+// ---- first layer: weight gradient straight from the BatchNorm backward's inputs (k_first_wgrad_bn) ------------------
+// A/B knob (environment SFOD_FIRST_WGRAD_FUSED, default 1): 0 makes the query refuse, i.e. the caller runs the two
+// launches (sfod_bn_relu_pool_bwd's apply pass, sfod_conv_wgrad_oihw).  Both give the same bits.
+static SfodKnob g_first_wgrad_fused{"SFOD_FIRST_WGRAD_FUSED", 1, sfod_knob_bool};
+extern "C" int sfod_set_first_wgrad_fused(int on) { g_first_wgrad_fused.set(on); return 0; }
+
+// the plan of the two-launch path when the fused kernel reproduces it, else ok = 0
+static W3Plan first_wgrad_bn_plan(int B, int H, int W, int Cin, int Cout, int pool, int dt, int y_dt) {
+  W3Plan p;
+  p.ok = 0;
+  if (!(conv_shape_fits(B, H, W, Cin, Cout, 3) && sfod_ints_ok({pool, dt, y_dt}))) return p;
+  if (Cin != 8 || Cout != 64 || pool != 0 || dt != SFOD_BF16X3 || y_dt != SFOD_F32) return p;
+  int nb = 0;
+  p = w3_plan_chunked(B, H, W, Cin, Cout, 3, Cout, dt, nb);
+  if (nb != B || !sfod_w3_bn_ok(p, Cin, Cout)) p.ok = 0;      // one sub-batch only: the batch's M is the BatchNorm's
+  return p;
+}
+
+extern "C" int sfod_conv_first_wgrad_bn_supported(int B, int H, int W, int Cin, int Cout, int pool, int dt, int y_dt) {
+  if (g_first_wgrad_fused.get() == 0) return 0;
+  return first_wgrad_bn_plan(B, H, W, Cin, Cout, pool, dt, y_dt).ok ? 1 : 0;
+}
+
+extern "C" int sfod_conv_first_wgrad_bn(const void* x, const void* dz, const void* y, const float* mean,
+                                        const float* invstd, const float* gamma, const float* beta,
+                                        const float* dgamma, const float* dbeta, float* dw, int B, int H, int W,
+                                        int Cin, int Cout, int dt, int oihw, int accumulate, void* ws,
+                                        int64_t ws_bytes, void* stream) {
+  sfod_note_conv_kernel(nullptr);      // the kernel record names this call's launch or nothing
+  SFOD_REQUIRE(conv_shape_fits(B, H, W, Cin, Cout, 3) && sfod_i64s_ok({ws_bytes}),
+               "conv_first_wgrad_bn: negative or oversized extent");
+  SFOD_REQUIRE(x != nullptr && dz != nullptr && y != nullptr && dw != nullptr, "conv_first_wgrad_bn: null operand");
+  SFOD_REQUIRE(mean && invstd && gamma && beta && dgamma && dbeta, "conv_first_wgrad_bn: null BatchNorm argument");
+  const W3Plan p = first_wgrad_bn_plan(B, H, W, Cin, Cout, 0, dt, SFOD_F32);
+  SFOD_REQUIRE(p.ok, "conv_first_wgrad_bn: shape not served (query sfod_conv_first_wgrad_bn_supported)");
+  SFOD_REQUIRE(ws != nullptr && ws_bytes >= p.ws_bytes, "conv_first_wgrad_bn: workspace too small (sfod_conv_wgrad_ws_bytes)");
+  W3BnApply bn;
+  bn.dz = (const float*)dz; bn.y = (const float*)y; bn.mean = mean; bn.invstd = invstd; bn.gamma = gamma; bn.beta = beta;
+  bn.dgamma = dgamma; bn.dbeta = dbeta;
+  // packed: added into, like sfod_conv_wgrad; OIHW: overwritten or added into, like sfod_conv_wgrad_oihw
+  const int out_mode = oihw ? (accumulate ? 2 : 1) : 0;
+  return sfod_w3_bn_launch(p, x, bn, dw, ws, B, H, W, out_mode, (hipStream_t)stream);
 }
 
 extern "C" int sfod_conv_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int Cin,

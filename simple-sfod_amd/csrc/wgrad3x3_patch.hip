@@ -576,6 +576,267 @@ k_wgrad3x3_patch(W3Args a) {
 }
 
 // =================================================================================================================
+// First layer (Cin = 8, Cout = 64, bf16x3 operands): the BatchNorm-backward apply pass fused into the weight gradient.
+//
+// conv1_1 has no data gradient, so its dy = BatchNorm'(dz, y) has one reader: this product.  The kernel reads dz and y
+// (fp32) instead, evaluates bn_bwd_unscaled + bn_bwd_pair (common.h: the expression and the pair of k_bn_bwd_apply<float, 0,
+// 1, split_t>) in registers and feeds the pairs to the MFMAs as the A operand: dy is never written or read back.
+//
+// The summation tree is the one of k_wgrad3x3_patch<4, true, .> above, so the slabs agree with it bit for bit: same tile
+// plan, same pixel splits, wave = (32-channel co fragment wco, k-step group kg), 64-pixel chunks in tile-pixel order,
+// k slot 8 h + j of the wave's k-step of chunk c = tile pixel 64 c + 16 kg + 8 h + j, per tap hi * lo, lo * hi, hi * hi
+// into one accumulator, pixels outside the tile or the image contribute dy = +0 (what the DMA's range check delivers
+// there), slab = split * 4 + kg.  What differs is how the operands arrive:
+//   dy   a lane of the A operand holds ONE output channel and 8 consecutive tile pixels: it loads its 8 dz and 8 y values
+//        with dword buffer loads (a half wave reads 128 contiguous bytes per pixel), two chunks ahead in registers; no LDS
+//   x    the 8-channel halo patch (12 KiB of data) is loaded one tile ahead into registers by 384 threads and stored into
+//        the 64-byte-row plane layout of the kernel above (channels 8..31 of every row stay zero), so the conflict-free
+//        transposed reads and the tap shifts apply unchanged; two buffers, ONE barrier per tile instead of one per chunk
+// No wave waits for another inside a tile, and 32 KiB of dz / y are in flight per CU.
+// =================================================================================================================
+constexpr int F1_TABP_OFF = 2 * XBUF;             // u16 [256]  tile pixel -> patch row (tap 0,0)
+constexpr int F1_TABT_OFF = F1_TABP_OFF + 512;    // u16 [256]  tile pixel -> ty << 8 | tx
+constexpr int F1_LDS_TOTAL = F1_TABT_OFF + 512;   // 99328
+
+struct W3BnArgs {
+  W3Args g;          // dy unused; Cin = 8, Cout = lddy = 64
+  W3BnApply bn;
+};
+
+typedef unsigned f1_u32x4 __attribute__((__vector_size__(16)));
+
+__global__ void __launch_bounds__(512)
+k_first_wgrad_bn(W3BnArgs fa) {
+  const W3Args& a = fa.g;
+  const W3BnApply& bn = fa.bn;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wco = wave & 1, kg = wave >> 1;
+  const int h = lane >> 5, g1 = (lane >> 4) & 1, t16 = lane & 15;
+  const int tq = t16 >> 2, tp = t16 & 3;
+  const int split = blockIdx.x;                    // one (co, ci) block: workgroup = pixel split
+  const int t_begin = split * a.tiles_per_split;
+  const int t_end = min(a.ntiles, t_begin + a.tiles_per_split);
+  const int PW = a.PW, TW = a.TW;
+  const int npix = a.TH * a.TW;
+
+  unsigned short* tabP = reinterpret_cast<unsigned short*>(smem + F1_TABP_OFF);
+  unsigned short* tabT = reinterpret_cast<unsigned short*>(smem + F1_TABT_OFF);
+  if (threadIdx.x < 256) {
+    const int p = threadIdx.x;
+    const int ty = p / TW, tx = p - ty * TW;      // ty <= 255 / 4, tx < TW <= 128
+    tabP[p] = (unsigned short)(p < npix ? ty * PW + tx : 0);
+    tabT[p] = (unsigned short)((ty << 8) | tx);
+  }
+  // both patch buffers start as zeros: the stores below only ever touch the first 16 bytes (channels 0..7) of a row
+  for (int i = threadIdx.x; i < 2 * XBUF / 16; i += 512) reinterpret_cast<f1_u32x4*>(smem)[i] = f1_u32x4{0u, 0u, 0u, 0u};
+  __syncthreads();
+
+  const int64_t npx = (int64_t)a.B * a.H * a.W;
+  const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)a.x, (short)0, (int)min((int64_t)0x7fffffff, npx * 32), 0x00020000);
+  const __amdgpu_buffer_rsrc_t zres = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)bn.dz, (short)0, (int)min((int64_t)0x7fffffff, npx * 256), 0x00020000);
+  const __amdgpu_buffer_rsrc_t yres = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)bn.y, (short)0, (int)min((int64_t)0x7fffffff, npx * 256), 0x00020000);
+
+  // this lane's output channel and its BatchNorm constants (the per-channel prologue of k_bn_bwd_apply)
+  const int co = wco * 32 + (lane & 31);
+  const float invM = 1.f / (float)npx;
+  const float invs = bn.invstd[co];
+  const float sc = invs * bn.gamma[co];
+  const float mu = bn.mean[co];
+  const float sh = bn.beta[co];
+  const float k1 = bn.dbeta[co] * invM;
+  const float k2 = bn.dgamma[co] * invM;
+
+  struct Org { int b, y0, x0; };
+  auto tile_origin = [&](int t) {
+    const int per = a.tiles_y * a.tiles_x;
+    Org o;
+    o.b = t / per;
+    const int r = t - o.b * per;
+    const int tyi = r / a.tiles_x;
+    o.y0 = tyi * a.TH;
+    o.x0 = (r - tyi * a.tiles_x) * a.TW;
+    return o;
+  };
+  auto advance = [&](Org o) {
+    o.x0 += a.TW;
+    if (o.x0 >= a.tiles_x * a.TW) {
+      o.x0 = 0;
+      o.y0 += a.TH;
+      if (o.y0 >= a.tiles_y * a.TH) { o.y0 = 0; ++o.b; }
+    }
+    return o;
+  };
+
+  // ---- x patch: thread r < 384 owns patch row r = (py, px); rows beyond the halo and pixels outside the image are zeros
+  const int prow_y = (int)threadIdx.x / PW, prow_x = (int)threadIdx.x - prow_y * PW;
+  const bool prow_ok = threadIdx.x < XROWS && prow_y < a.TH + 2;
+  f1_u32x4 phi = {0u, 0u, 0u, 0u}, plo = {0u, 0u, 0u, 0u};
+  // `live` false (no next tile) and threads without a row: every lane's offset is out of range, nothing is fetched.  The
+  // loads themselves are unconditional: a conditional redefinition of registers that loads are in flight into makes the
+  // compiler copy them at the join, behind a wait for ALL outstanding loads.
+  auto patch_load = [&](Org o, bool live) {
+    const int iy = o.y0 - 1 + prow_y, ix = o.x0 - 1 + prow_x;
+    const bool ok = live & prow_ok & (iy >= 0) & (iy < a.H) & (ix >= 0) & (ix < a.W);
+    const unsigned in = (unsigned)(((o.b * a.H + iy) * a.W + ix) * 32);
+    const unsigned off = ok ? in : OOB_OFF;
+    phi = __builtin_amdgcn_raw_buffer_load_b128(xres, (int)off, 0, 0);
+    plo = __builtin_amdgcn_raw_buffer_load_b128(xres, (int)(off + 16u), 0, 0);
+  };
+  auto patch_store = [&](int buf) {
+    if (threadIdx.x < XROWS) {
+      *reinterpret_cast<f1_u32x4*>(smem + buf * XBUF + threadIdx.x * 64) = phi;
+      *reinterpret_cast<f1_u32x4*>(smem + buf * XBUF + XPLANE + threadIdx.x * 64) = plo;
+    }
+  };
+  // the patch stores of this wave are in LDS, then every wave's are: the transposed reads (asm) may follow
+  auto lds_barrier = [&]() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+
+  // ---- dz / y of the wave's k-step of chunk c: tile pixels 64 c + 16 kg + 8 h + j, j = 0..7, channel co
+  struct Raw { float z[8], v[8]; unsigned ok; };
+  auto chunk_load = [&](Org o, auto cc, Raw& r, bool live) {
+    constexpr int c = decltype(cc)::value;
+    const int p0 = c * 64 + kg * 16 + 8 * h;
+    const unsigned tt = tabT[p0];
+    int ty = (int)(tt >> 8), tx = (int)(tt & 255u);
+    unsigned okm = 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool ok = live & (p0 + j < npix) & (o.y0 + ty < a.H) & (o.x0 + tx < a.W);
+      const unsigned in = (unsigned)((((o.b * a.H + o.y0 + ty) * a.W + o.x0 + tx) * 64 + co) * 4);
+      const unsigned off = ok ? in : OOB_OFF;
+      r.z[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(zres, (int)off, 0, 0));
+      r.v[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(yres, (int)off, 0, 0));
+      okm |= ok ? (1u << j) : 0u;
+      if (++tx == TW) { tx = 0; ++ty; }
+    }
+    r.ok = okm;
+  };
+
+  f32x16 acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+  const int cbb = (g1 * 16 + 4 * tp) * 2;          // byte column inside a 64-byte plane row
+
+  // dy pairs of one k-step from the raw values (frees the raw set for the chunk two ahead)
+  bf16x8 ah, al;
+  auto form = [&](const Raw& r) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      // opaque here: instruction selection otherwise floats this arithmetic up to the loads (it has no ordering against
+      // the barriers above), which turns the prefetch into load-and-wait
+      float vj = r.v[j], zj = r.z[j];
+      asm volatile("" : "+v"(vj), "+v"(zj));
+      const float e = bn_bwd_unscaled<1>(vj, zj, mu, invs, sc, sh, k1, k2);
+      bf16_t hh, ll;
+      bn_bwd_pair(sc, e, hh, ll);
+      const bool in = (r.ok >> j) & 1u;                      // selects: pixels outside the tile / the image are +0
+      ah[j] = in ? hh : (bf16_t)0.f;
+      al[j] = in ? ll : (bf16_t)0.f;
+    }
+  };
+  // the 27 MFMAs of k_wgrad3x3_patch<4, true>'s k-step, in its order
+  auto kstep = [&](auto cc, int xb_off) {
+    constexpr int c = decltype(cc)::value;
+    const int pp = c * 64 + kg * 16 + 8 * h + tq;
+    const unsigned rx0 = (unsigned)(xb_off + tabP[pp] * 64 + cbb);
+    const unsigned rx1 = (unsigned)(xb_off + tabP[pp + 4] * 64 + cbb);
+    // fragments of ONE tap per buffer, two buffers (the raw dz / y sets need the registers of a whole filter row): tap
+    // t + 1 is requested in front of tap t's three MFMAs.  Taps own their accumulators, so their order is free.
+    s16x4 q[2][4];    // (rx0, rx1) of the hi plane, then of the lo plane
+    auto issue_tap = [&](s16x4* d, unsigned r0, unsigned r1) {
+      d[0] = tr_read<0>(r0);      d[1] = tr_read<0>(r1);
+      d[2] = tr_read<XPLANE>(r0); d[3] = tr_read<XPLANE>(r1);
+    };
+    issue_tap(q[0], rx0, rx1);
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      if (t < 8) {
+        const unsigned sft = (unsigned)((((t + 1) / 3) * PW + (t + 1) % 3) * 64);
+        issue_tap(q[(t + 1) & 1], rx0 + sft, rx1 + sft);
+        wait_lgkm<4>();
+      } else {
+        wait_lgkm<0>();
+      }
+      const s16x4* d = q[t & 1];
+      const bf16x8 bh = cat8(d[0], d[1]), bl = cat8(d[2], d[3]);
+      f32x16 v = acc[t];
+      v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, v, 0, 0, 0);
+      v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, v, 0, 0, 0);
+      v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, v, 0, 0, 0);
+      acc[t] = v;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  if (t_begin < t_end) {
+    Org cur = tile_origin(t_begin);
+    Raw r0, r1;
+    patch_load(cur, true);
+    chunk_load(cur, IC<0>{}, r0, true);
+    chunk_load(cur, IC<1>{}, r1, true);
+    patch_store(0);
+    lds_barrier();
+    for (int t = t_begin; t < t_end; ++t) {
+      const Org nxt = advance(cur);
+      const bool more = (t + 1 < t_end);
+      const int xb_off = ((t - t_begin) & 1) * XBUF;
+      patch_load(nxt, more);
+      __builtin_amdgcn_sched_barrier(0);
+      // chunk c is consumed from the raw set c & 1, which then receives the chunk two ahead.  The scheduling barriers
+      // keep the loads where they are written: at the register limit the scheduler otherwise moves every load down to
+      // its first use (shorter live ranges), i.e. no prefetch at all.
+      form(r0);
+      __builtin_amdgcn_sched_barrier(0);
+      chunk_load(cur, IC<2>{}, r0, true);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(IC<0>{}, xb_off);
+      form(r1);
+      __builtin_amdgcn_sched_barrier(0);
+      chunk_load(cur, IC<3>{}, r1, true);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(IC<1>{}, xb_off);
+      form(r0);
+      __builtin_amdgcn_sched_barrier(0);
+      chunk_load(nxt, IC<0>{}, r0, more);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(IC<2>{}, xb_off);
+      form(r1);
+      __builtin_amdgcn_sched_barrier(0);
+      chunk_load(nxt, IC<1>{}, r1, more);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(IC<3>{}, xb_off);
+      // the next tile's patch goes into the other buffer (last read one tile ago, before the previous barrier)
+      patch_store(((t - t_begin) & 1) ^ 1);      // zeros after the last tile
+      lds_barrier();
+      cur = nxt;
+    }
+  }
+
+  const int slab_idx = split * 4 + kg;
+  float* out = a.slab + (int64_t)slab_idx * a.Cout * 9 * a.Cin;
+  const int ci = lane & 31;
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int oc = wco * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (oc < a.Cout && ci < a.Cin) out[((int64_t)oc * 9 + t) * a.Cin + ci] = acc[t][r];
+    }
+}
+
+// =================================================================================================================
 // W64 (bf16x3 operands, round 3): a 64 co x 64 ci block per workgroup on 128-pixel tiles.
 //
 // The knock-out runs of the 64 x 32 kernel above (profiles/r3_wgrad_knockout.txt) say what bounds it: not the matrix
@@ -1008,6 +1269,8 @@ W3Plan sfod_w3_plan(int B, int H, int W, int Cin, int Cout, int lddy, int split)
   return p;
 }
 
+static int w3_reduce_launch(const W3Plan& p, void* ws, float* dw, int Cin, int Cout, int out_mode, hipStream_t s);
+
 // split != 0 (SFOD_BF16X3): x / dy hold (hi, lo) pairs; Cin / Cout / lddy are LOGICAL channel counts in either case
 int sfod_w3_launch(const W3Plan& p, const void* x, const void* dy, float* dw, void* ws, int B, int H, int W,
                    int Cin, int Cout, int lddy, int out_mode, hipStream_t s, int split) {
@@ -1043,6 +1306,11 @@ int sfod_w3_launch(const W3Plan& p, const void* x, const void* dy, float* dw, vo
   else hipLaunchKernelGGL(k_wgrad3x3_patch<2>, grid, blk, LDS_TOTAL, s, a);
   int rc = sfod_check_launch("wgrad3x3_patch");
   if (rc) return rc;
+  return w3_reduce_launch(p, ws, dw, Cin, Cout, out_mode, s);
+}
+
+// slabs -> dw in slab order (out_mode as sfod_w3_launch)
+static int w3_reduce_launch(const W3Plan& p, void* ws, float* dw, int Cin, int Cout, int out_mode, hipStream_t s) {
   const int64_t n = (int64_t)Cout * 9 * Cin;  // multiple of 4 (Cin % 32 == 0; bf16x3: Cin % 8 == 0)
   const int64_t n4 = n / 4;
   const bool wide = true;                           // slabs spread over 8 groups per workgroup (more loads in flight)
@@ -1061,4 +1329,33 @@ int sfod_w3_launch(const W3Plan& p, const void* x, const void* dy, float* dw, vo
   else RED_LAUNCH(2);
 #undef RED_LAUNCH
   return sfod_check_launch("wgrad_reduce");
+}
+
+// ---- first layer: BatchNorm-backward apply fused in (k_first_wgrad_bn) ---------------------------------------------
+// the plan must be the 64 x 32-block one of the bf16x3 operands (four k-step groups) with a single (co, ci) block
+bool sfod_w3_bn_ok(const W3Plan& p, int Cin, int Cout) {
+  return p.ok && !p.w64 && p.CO == 4 && Cin == 8 && Cout == 64 && p.co_tiles == 1 && p.ci_tiles == 1 &&
+         p.nslab == 4 * p.nsplit && p.TH * p.TW <= 256 && (p.TH + 2) * (p.TW + 2) <= XROWS;
+}
+
+int sfod_w3_bn_launch(const W3Plan& p, const void* x, const W3BnApply& bn, float* dw, void* ws, int B, int H, int W,
+                      int out_mode, hipStream_t s) {
+  W3BnArgs fa;
+  W3Args& a = fa.g;
+  a.x = (const bf16_t*)x; a.dy = nullptr; a.slab = (float*)ws;
+  a.B = B; a.H = H; a.W = W; a.Cin = 8; a.Cout = 64; a.lddy = 64;
+  a.TH = p.TH; a.TW = p.TW; a.PW = p.TW + 2;
+  a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x;
+  a.ntiles = B * p.tiles_y * p.tiles_x;
+  a.tiles_per_split = p.tiles_per_split;
+  a.co_tiles = 1; a.ci_tiles = 1; a.nsplit = p.nsplit;
+  fa.bn = bn;
+  static const hipError_t attr_rc =
+      hipFuncSetAttribute((const void*)k_first_wgrad_bn, hipFuncAttributeMaxDynamicSharedMemorySize, F1_LDS_TOTAL);
+  if (attr_rc != hipSuccess) { sfod_set_error("hipFuncSetAttribute(first_wgrad_bn): %s", hipGetErrorString(attr_rc)); return -(int)attr_rc; }
+  sfod_note_conv_kernel("k_first_wgrad_bn");
+  hipLaunchKernelGGL(k_first_wgrad_bn, dim3(p.nsplit), dim3(512), F1_LDS_TOTAL, s, fa);
+  const int rc = sfod_check_launch("first_wgrad_bn");
+  if (rc) return rc;
+  return w3_reduce_launch(p, ws, dw, 8, 64, out_mode, s);
 }

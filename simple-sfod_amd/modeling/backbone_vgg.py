@@ -326,13 +326,17 @@ class vgg_backbone(nn.Module):
             # (grad_sink): no temporaries, no per-parameter accumulate kernels in autograd
             gsink, bsink = native.grad_sink(bn.weight), native.grad_sink(bn.bias)
             direct_bn = gsink is not None and bsink is not None
+            # conv1_1 has no data gradient: its dy would be written for ONE reader, the weight gradient.  Where the library
+            # serves it, that kernel forms dy from dz and y itself (same bits) and the apply pass and the dy tensor go away
+            first_fused = li == 0 and native.conv_first_wgrad_bn_supported(x, y, conv.out_channels, pool)
             dy, dgamma, dbeta = native.bn_relu_pool_bwd(dz, y, mean, invstd, bn.weight.detach(),
                                                         bn.bias.detach(), pool,
                                                         dgamma_acc=gsink if direct_bn else None,
                                                         dbeta_acc=bsink if direct_bn else None,
                                                         out_dtype=dtype,    # bf16x3: dz / y fp32 -> dy pairs
-                                                        reduced=dz_red)
+                                                        reduced=dz_red, apply=not first_fused)
             dz_red = None
+            dsum = (dgamma, dbeta)      # this call's finalized sums (also when they went into the accumulators)
             if direct_bn:
                 dgamma = dbeta = None
             cout, cin = conv.out_channels, conv.in_channels
@@ -340,7 +344,12 @@ class vgg_backbone(nn.Module):
             # goes on with the data gradient.  Their memory belongs to the main stream's pool: record_stream tells the
             # allocator not to hand it out again before the side kernel has run, so the references can be dropped
             # layer by layer (holding all 13 (x, dy) pairs until the join cost ~180 MB per image and layer at conv1_x)
-            dw = off.run(lambda: native.conv_weight_grad(x, dy, conv.weight), x, dy)
+            if first_fused:
+                dw = off.run(lambda: native.conv_first_weight_grad(x, dz, y, mean, invstd, bn.weight.detach(),
+                                                                   bn.bias.detach(), *dsum, conv.weight),
+                             x, dz, y, mean, invstd, *dsum)
+            else:
+                dw = off.run(lambda: native.conv_weight_grad(x, dy, conv.weight), x, dy)
             # a conv bias followed by train-mode BN has an analytically zero gradient
             # (sum_rows dy == 0); the reference's autograd produces rounding noise around 0.
             db = None if native.grad_sink(conv.bias) is not None else torch.zeros_like(conv.bias)

@@ -883,6 +883,60 @@ def conv_weight_grad(x, dy, weight, operand=None):
     return dw
 
 
+def set_first_wgrad_fused(on):
+    """conv1_1's weight gradient: 1 (default) straight from the BatchNorm backward's inputs (``conv_first_wgrad_bn``), 0 the
+    apply pass + ``conv_weight_grad``.  Same bits either way (A/B knob, include/sfod_hip.h)."""
+    load().sfod_set_first_wgrad_fused(int(on))
+
+
+def conv_first_wgrad_bn_supported(x, y, cout, pool, relu=True):
+    """whether ``conv_first_wgrad_bn`` reproduces ``bn_relu_pool_bwd`` (dy as bf16 pairs) + ``conv_wgrad_oihw`` for the layer
+    with weight-gradient operand ``x`` and saved pre-BatchNorm output ``y`` (first layer, bf16 pairs, ReLU, no pooling)"""
+    if x is None or x.dim() != 4 or y.dim() != 4 or not x.is_cuda or tuple(y.shape) != (*x.shape[:3], cout):
+        return False
+    B, H, W, cin = x.shape
+    return bool(query("sfod_conv_first_wgrad_bn_supported", B, H, W, cin, cout, int(pool) | (0 if relu else 2),
+                      dt_of(x), dt_of(y)))
+
+
+def conv_first_wgrad_bn(x, dz, y, mean, invstd, gamma, beta, dgamma, dbeta, dw, accumulate=False):
+    """The 3x3 weight gradient of the first layer from dz / y and the finalized ``dgamma`` / ``dbeta`` of
+    ``bn_relu_pool_bwd(..., apply=False)``, bit-identical to the apply pass followed by ``conv_wgrad`` (``dw`` packed
+    [Cout, 9, Cin], always added into) or ``conv_wgrad_oihw`` (``dw`` OIHW, overwritten or added into)."""
+    B, H, W, cin = x.shape
+    oihw = dw.dim() == 4
+    cout = dw.shape[0]
+    assert tuple(dw.shape) == ((cout, cin, 3, 3) if oihw else (cout, 9, cin))
+    assert dw.is_contiguous() and dw.dtype == torch.float32
+    assert dz.dtype == torch.float32 and y.dtype == torch.float32 and dz.shape == y.shape == (B, H, W, cout)
+    dt = dt_of(x)
+    nbytes = query("sfod_conv_wgrad_ws_bytes", B, H, W, cin, cout, 3, cout, dt)
+    ws = _workspace(x.device, nbytes)
+    call("sfod_conv_first_wgrad_bn", x, dz, y, mean, invstd, gamma, beta, dgamma, dbeta, dw, B, H, W, cin, cout, dt,
+         int(oihw), int(accumulate), ws, nbytes, timer_name="sfod_conv_wgrad_oihw" if oihw else "sfod_conv_wgrad",
+         flops=2.0 * B * H * W * cout * 9 * cin)
+    return dw
+
+
+def conv_first_weight_grad(x, dz, y, mean, invstd, gamma, beta, dgamma, dbeta, weight):
+    """``conv_weight_grad(x, dy, weight)`` of the first layer with dy formed inside the kernel (``conv_first_wgrad_bn``): the
+    same route into ``grad_sink(weight)`` / a new tensor, so the same bits."""
+    cout, cin, _, _ = weight.shape
+    sink = grad_sink(weight)
+    args = (x, dz, y, mean, invstd, gamma, beta, dgamma, dbeta)
+    if sink is not None and x.shape[-1] == cin:
+        conv_first_wgrad_bn(*args, sink, accumulate=True)
+        return None
+    dwp = torch.zeros(cout, 9, x.shape[-1], dtype=torch.float32, device=x.device)
+    conv_first_wgrad_bn(*args, dwp)
+    if sink is not None:
+        unpack_conv_wgrad(dwp, sink, accumulate=True)
+        return None
+    dw = torch.empty_like(weight)
+    unpack_conv_wgrad(dwp, dw)
+    return dw
+
+
 def bias_grad(dy, n, db=None, accumulate=False):
     m = dy.numel() // dy.shape[-1]
     if db is None:
@@ -938,12 +992,15 @@ def bn_add_relu_fwd(y, mean, invstd, gamma, beta, residual, with_operand=None, w
 
 
 def bn_relu_pool_bwd(dz, y, mean, invstd, gamma, beta, pool, dgamma=None, dbeta=None, dy=None, relu=True,
-                     dgamma_acc=None, dbeta_acc=None, out_dtype=None, reduced=None):
+                     dgamma_acc=None, dbeta_acc=None, out_dtype=None, reduced=None, apply=True):
     """``dgamma_acc`` / ``dbeta_acc``: gradient accumulators (see ``grad_sink``) updated in the same launch.
     ``out_dtype``: dtype of dy (y.dtype, or SPLIT_DTYPE from fp32 inputs: dy only feeds the wgrad / dgrad MFMAs).
-    ``reduced``: the partial-sum workspace ``conv_dgrad_bnred`` returned with dz -- the reduction pass is skipped."""
+    ``reduced``: the partial-sum workspace ``conv_dgrad_bnred`` returned with dz -- the reduction pass is skipped.
+    ``apply`` False: the sums only (same reduction, same finalize), no dy is allocated or written -> (None, dgamma, dbeta);
+    for a layer whose dy is formed by its consumer (``conv_first_wgrad_bn``)."""
     B, H, W, C = y.shape
-    if dy is None:
+    dy_dt = dt_of_dtype(out_dtype or y.dtype) if dy is None else dt_of(dy)
+    if dy is None and apply:
         dy = torch.empty(y.shape, dtype=out_dtype or y.dtype, device=y.device)
     if dgamma is None:
         dgamma = torch.empty(C, dtype=torch.float32, device=y.device)
@@ -956,7 +1013,7 @@ def bn_relu_pool_bwd(dz, y, mean, invstd, gamma, beta, pool, dgamma=None, dbeta=
         ws, nred = torch.empty(query("sfod_bn_bwd_ws_floats", B * H * W, C), dtype=torch.float32, device=y.device), 0
     call("sfod_bn_relu_pool_bwd", dz, y, mean, invstd, gamma, beta, dy, dgamma, dbeta, dgamma_acc, dbeta_acc, ws,
          B, H, W, C,
-         int(pool) | (0 if relu else 2), dt_of(y), dt_of(dy), nred)
+         int(pool) | (0 if relu else 2), dt_of(y), dy_dt, nred)
     return dy, dgamma, dbeta
 
 
