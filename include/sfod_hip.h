@@ -409,6 +409,20 @@ int sfod_rpn_decode(const float* rpn_out, int ld, const float* cell_anchors, int
 int sfod_rpn_decode_opt(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
                         int Wf, int stride, const int32_t* image_sizes, float* props, float* scores,
                         int32_t* flags, float wx, float wy, float ww, float wh, void* stream);
+/* ---- Proposal and matcher options (MODEL.ANCHOR_GENERATOR.OFFSET, MODEL.RPN.BOUNDARY_THRESH,
+ * MODEL.PROPOSAL_GENERATOR.MIN_SIZE, MODEL.ROI_HEADS.IOU_THRESHOLDS / IOU_LABELS).  The entry points that rebuild the
+ * anchors in registers (sfod_rpn_decode_shift, sfod_anchor_match_opt, sfod_rpn_loss_shift) take, by value:
+ *   shift   float32(OFFSET * stride): the caller's product of two python doubles rounded ONCE (the convention of
+ *           ema_one_minus_keep below; float32(OFFSET) * stride rounds twice and differs, e.g. for OFFSET 0.3, stride 16).
+ *           Anchor (y, x, a) = cell_anchors[a] + (sx, sy, sx, sy) with sx = shift + (float)(x * stride),
+ *           sy = shift + (float)(y * stride): one fp32 add each, no contraction -- the float32
+ *           torch.arange(offset * stride, n * stride, step=stride) of d2's _create_grid_offsets.  shift must be 0 or finite
+ *           and inside (0, stride), else SFOD_EBADARG.  shift 0 gives the bits of the forms without it (0.f + v == v).
+ * Every pointer, extent and float of these entry points is checked before anything is launched.
+ * sfod_rpn_decode_shift: sfod_rpn_decode_opt with `shift`; sfod_rpn_decode_opt is this call with shift 0. */
+int sfod_rpn_decode_shift(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
+                          int Wf, int stride, const int32_t* image_sizes, float* props, float* scores,
+                          int32_t* flags, float wx, float wy, float ww, float wh, float shift, void* stream);
 /* stable descending segmented sort of B segments of n floats; out_idx int32 [B,n].
  * ws: workspace of sfod_sort_ws_bytes(B,n) bytes. */
 int64_t sfod_sort_ws_bytes(int B, int n);
@@ -418,6 +432,12 @@ int sfod_segmented_sort_desc(const float* keys, int B, int n, float* out_keys, i
 int sfod_rpn_gather_topk(const float* props, const float* sorted_scores, const int32_t* sorted_idx,
                          int B, int NA, int k, float* cand_boxes, float* cand_scores,
                          uint8_t* cand_valid, void* stream);
+/* General form: min_size = MODEL.PROPOSAL_GENERATOR.MIN_SIZE, finite and >= 0 (else SFOD_EBADARG):
+ * valid = (x2 - x1) > min_size && (y2 - y1) > min_size on the clipped box, strict (d2 Boxes.nonempty(threshold)).
+ * sfod_rpn_gather_topk is this call with 0. */
+int sfod_rpn_gather_topk_opt(const float* props, const float* sorted_scores, const int32_t* sorted_idx,
+                             int B, int NA, int k, float min_size, float* cand_boxes, float* cand_scores,
+                             uint8_t* cand_valid, void* stream);
 
 /* ---- K8/K16: greedy NMS.  tv nms / batched_nms via d2 batched_nms (Appendix A.6):
  * boxes already sorted by descending score; suppress j>i when IoU > thr (strict, fp32, no +1).
@@ -444,12 +464,30 @@ int sfod_gather_kept(const float* cand_boxes, const float* cand_scores, const in
 int sfod_anchor_match(const float* cell_anchors, int A, int B, int Hf, int Wf, int stride,
                       const float* gt_boxes, const int32_t* gt_count, int Gcap, float lo, float hi,
                       int32_t* matched, int8_t* labels, float* gtmax, void* stream);
+/* General form: `shift` (above) and MODEL.RPN.BOUNDARY_THRESH.  image_sizes: int32 [B,2] as (h, w), the layout
+ * sfod_rpn_decode reads.  With t = boundary_thresh >= 0, AFTER the matcher's label (low-quality promotion included, and also
+ * for an image without ground truth, whose anchors are all 0) an anchor is relabelled -1 unless
+ *   x1 >= -t && y1 >= -t && x2 < w + t && y2 < h + t            (d2 Boxes.inside_box, fp32, on the anchor built above).
+ * boundary_thresh < 0: the test is off and image_sizes may be NULL; >= 0 with NULL image_sizes, NaN or +inf: SFOD_EBADARG.
+ * `matched` does not depend on it.  sfod_anchor_match is this call with shift 0, boundary_thresh -1, NULL. */
+int sfod_anchor_match_opt(const float* cell_anchors, int A, int B, int Hf, int Wf, int stride,
+                          const float* gt_boxes, const int32_t* gt_count, int Gcap, float lo, float hi,
+                          float shift, float boundary_thresh, const int32_t* image_sizes, int32_t* matched,
+                          int8_t* labels, float* gtmax, void* stream);
 /* ROI version: boxes [B,P,4] with count; one threshold; writes the class target:
  * cls[b][p] = gt_classes[matched] if IoU>=thr else num_classes; -2 for p >= count. */
 int sfod_roi_match(const float* boxes, const int32_t* box_count, int B, int P,
                    const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_count,
                    int Gcap, float thr, int num_classes, int32_t* matched, int32_t* cls,
                    void* stream);
+/* General form: d2 Matcher with thresholds [lo, hi] / labels [0, -1, 1] followed by _sample_proposals' class targets:
+ *   cls[b][p] = best >= hi ? gt_classes[matched] : (best >= lo ? -1 : num_classes),   best = max IoU over the image's GT;
+ * -2 for p >= count; an image without ground truth stays all num_classes.  lo, hi finite, lo <= hi (else SFOD_EBADARG).
+ * sfod_subsample mode 1 never samples a -1.  sfod_roi_match is this call with lo == hi == thr ([thr] / [0, 1]). */
+int sfod_roi_match_opt(const float* boxes, const int32_t* box_count, int B, int P,
+                       const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_count,
+                       int Gcap, float lo, float hi, int num_classes, int32_t* matched, int32_t* cls,
+                       void* stream);
 /* ---- K10: subsample_labels (Appendix A.9).  The random choice is an INPUT: one uint32 key per
  * element; the sample is the n candidates with the smallest (key, index).
  * mode 0 (RPN, _subsample_labels): labels int8 in/out [B,n]: positives = 1, negatives = 0,
@@ -492,6 +530,12 @@ int sfod_rpn_loss_opt(const float* rpn_out, int ld, const float* cell_anchors, i
                       const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
                       float* loss, const float* grad_scale, float* d_rpn_out, float* ws, float wx, float wy,
                       float ww, float wh, int loss_type, float beta, void* stream);
+/* sfod_rpn_loss_opt with the anchor `shift` (Proposal and matcher options, above); sfod_rpn_loss_opt is this call with 0. */
+int sfod_rpn_loss_shift(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
+                        int Wf, int stride, const int8_t* labels, const int32_t* matched,
+                        const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
+                        float* loss, const float* grad_scale, float* d_rpn_out, float* ws, float wx, float wy,
+                        float ww, float wh, int loss_type, float beta, float shift, void* stream);
 
 /* concat proposals and GT boxes: d2 add_ground_truth_to_proposals (roi_heads.py:170) */
 int sfod_append_gt(const float* props, const int32_t* prop_count, int B, int P,

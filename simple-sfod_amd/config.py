@@ -167,17 +167,20 @@ def get_cfg():
     _C.MODEL.FPN.FUSE_TYPE = "sum"
     _C.MODEL.PROPOSAL_GENERATOR = CN()
     _C.MODEL.PROPOSAL_GENERATOR.NAME = "RPN"
+    # Proposal and matcher options (modeling/proposal_options.py).  Built: MIN_SIZE >= 0, ANCHOR_GENERATOR.OFFSET in [0, 1),
+    # RPN.BOUNDARY_THRESH -1 (off) or >= 0, ROI_HEADS.IOU_THRESHOLDS / IOU_LABELS [t] / [0, 1] or [lo, hi] / [0, -1, 1].
+    # Not built (ValueError naming the key): another ANCHOR_GENERATOR.NAME, RPN.HEAD_NAME, RPN.CONV_DIMS or RPN.IOU_LABELS.
     _C.MODEL.PROPOSAL_GENERATOR.MIN_SIZE = 0
     _C.MODEL.ANCHOR_GENERATOR = CN()
-    _C.MODEL.ANCHOR_GENERATOR.NAME = "DefaultAnchorGenerator"
+    _C.MODEL.ANCHOR_GENERATOR.NAME = "DefaultAnchorGenerator"      # the only one built
     _C.MODEL.ANCHOR_GENERATOR.SIZES = [[32, 64, 128, 256, 512]]
     _C.MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS = [[0.5, 1.0, 2.0]]
     _C.MODEL.ANCHOR_GENERATOR.ANGLES = [[-90, 0, 90]]
-    _C.MODEL.ANCHOR_GENERATOR.OFFSET = 0.0
+    _C.MODEL.ANCHOR_GENERATOR.OFFSET = 0.0                         # grid shift in strides, [0, 1)
     _C.MODEL.RPN = CN()
-    _C.MODEL.RPN.HEAD_NAME = "StandardRPNHead"
+    _C.MODEL.RPN.HEAD_NAME = "StandardRPNHead"                     # the only one built
     _C.MODEL.RPN.IN_FEATURES = ["res4"]
-    _C.MODEL.RPN.BOUNDARY_THRESH = -1
+    _C.MODEL.RPN.BOUNDARY_THRESH = -1                              # -1: off; t >= 0: anchors > t pixels outside get label -1
     _C.MODEL.RPN.IOU_THRESHOLDS = [0.3, 0.7]
     _C.MODEL.RPN.IOU_LABELS = [0, -1, 1]
     _C.MODEL.RPN.BATCH_SIZE_PER_IMAGE = 256
@@ -192,7 +195,7 @@ def get_cfg():
     _C.MODEL.RPN.POST_NMS_TOPK_TRAIN = 2000
     _C.MODEL.RPN.POST_NMS_TOPK_TEST = 1000
     _C.MODEL.RPN.NMS_THRESH = 0.7
-    _C.MODEL.RPN.CONV_DIMS = [-1]
+    _C.MODEL.RPN.CONV_DIMS = [-1]                                  # the only value built
     _C.MODEL.ROI_HEADS = CN()
     _C.MODEL.ROI_HEADS.NAME = "Res5ROIHeads"
     _C.MODEL.ROI_HEADS.NUM_CLASSES = 80

@@ -44,11 +44,14 @@ __device__ __forceinline__ bool nms_suppresses(Box a, Box b, float thr) {
   return (inter / ((sa + sb) - inter)) > thr;
 }
 
-__device__ __forceinline__ Box anchor_at(const float* cell, int A, int Wf, int stride, int i) {
+// Anchor i of the (y, x, a) grid, rebuilt in registers.  shift = float32(MODEL.ANCHOR_GENERATOR.OFFSET * stride), by value:
+// one fp32 add per axis (no contraction in this file), the float32 torch.arange(offset * stride, n * stride, stride) of d2's
+// _create_grid_offsets.  shift 0 gives the bits of the form without it (0.f + v == v).
+__device__ __forceinline__ Box anchor_at(const float* cell, int A, int Wf, int stride, float shift, int i) {
   int a = i % A;
   int p = i / A;
   int x = p % Wf, y = p / Wf;
-  float sx = (float)(x * stride), sy = (float)(y * stride);
+  float sx = shift + (float)(x * stride), sy = shift + (float)(y * stride);
   return Box{sx + cell[a * 4 + 0], sy + cell[a * 4 + 1], sx + cell[a * 4 + 2], sy + cell[a * 4 + 3]};
 }
 
@@ -95,6 +98,11 @@ struct BoxWeights {
 #define BOXREG_SMOOTH_L1 0
 #define BOXREG_GIOU 1
 #define GIOU_EPS 1e-7f
+
+// anchor shift of the `_shift` / `_opt` entry points: 0 (any stride, the forms without it), else finite and inside (0, stride)
+static inline bool sfod_anchor_shift_ok(float shift, int stride) {
+  return shift == 0.f || (isfinite(shift) && shift > 0.f && shift < (float)stride);
+}
 
 static inline bool sfod_box_weights_ok(float wx, float wy, float ww, float wh) {
   return isfinite(wx) && isfinite(wy) && isfinite(ww) && isfinite(wh) && wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f;
@@ -176,7 +184,8 @@ __device__ __forceinline__ float box_reg_term(Box src, Box gt, const float* d, B
 // ---------------------------------------------------------------------------------------------
 __global__ void k_rpn_decode(const float* __restrict__ rpn_out, int ld, const float* __restrict__ cell,
                              int A, int Hf, int Wf, int stride, const int32_t* __restrict__ sizes,
-                             float* __restrict__ props, float* __restrict__ scores, int32_t* flags, BoxWeights bw) {
+                             float* __restrict__ props, float* __restrict__ scores, int32_t* flags, BoxWeights bw,
+                             float shift) {
   const int b = blockIdx.y;
   const int NA = Hf * Wf * A;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -185,7 +194,7 @@ __global__ void k_rpn_decode(const float* __restrict__ rpn_out, int ld, const fl
   const float* row = rpn_out + ((int64_t)b * Hf * Wf + p) * ld;
   const float logit = row[a];
   const float* d = row + A + a * 4;
-  Box anc = anchor_at(cell, A, Wf, stride, i);
+  Box anc = anchor_at(cell, A, Wf, stride, shift, i);
   Box pb = apply_deltas(anc, d[0], d[1], d[2], d[3], bw.x, bw.y, bw.w, bw.h);
   bool fin = isfinite(pb.x1) && isfinite(pb.y1) && isfinite(pb.x2) && isfinite(pb.y2) && isfinite(logit);
   if (!fin) atomicOr(flags, 1);
@@ -194,12 +203,13 @@ __global__ void k_rpn_decode(const float* __restrict__ rpn_out, int ld, const fl
   scores[(int64_t)b * NA + i] = logit;
 }
 
-extern "C" int sfod_rpn_decode_opt(const float* rpn_out, int ld, const float* cell_anchors, int A, int B,
-                                   int Hf, int Wf, int stride, const int32_t* image_sizes, float* props,
-                                   float* scores, int32_t* flags, float wx, float wy, float ww, float wh,
-                                   void* stream) {
+extern "C" int sfod_rpn_decode_shift(const float* rpn_out, int ld, const float* cell_anchors, int A, int B,
+                                     int Hf, int Wf, int stride, const int32_t* image_sizes, float* props,
+                                     float* scores, int32_t* flags, float wx, float wy, float ww, float wh,
+                                     float shift, void* stream) {
   SFOD_REQUIRE_EXTENTS("rpn_decode", ld, A, B, Hf, Wf, stride);
   SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "rpn_decode: box weights must be finite and > 0");
+  SFOD_REQUIRE(sfod_anchor_shift_ok(shift, stride), "rpn_decode: anchor shift must be finite and in [0, stride)");
   SFOD_REQUIRE(sfod_prod_fits({Hf, Wf, A}) && sfod_prod_fits({5, A}) && sfod_prod_fits({B, Hf, Wf, ld}, 1LL << 40),
                "rpn_decode: oversized anchor grid");
   SFOD_REQUIRE(rpn_out && cell_anchors && image_sizes && props && scores && flags, "rpn_decode: null argument");
@@ -207,8 +217,16 @@ extern "C" int sfod_rpn_decode_opt(const float* rpn_out, int ld, const float* ce
   const int NA = Hf * Wf * A;
   dim3 grid(cdiv(NA, 256), B);
   hipLaunchKernelGGL(k_rpn_decode, grid, dim3(256), 0, (hipStream_t)stream, rpn_out, ld, cell_anchors,
-                     A, Hf, Wf, stride, image_sizes, props, scores, flags, BoxWeights{wx, wy, ww, wh});
+                     A, Hf, Wf, stride, image_sizes, props, scores, flags, BoxWeights{wx, wy, ww, wh}, shift);
   return sfod_check_launch("rpn_decode");
+}
+
+extern "C" int sfod_rpn_decode_opt(const float* rpn_out, int ld, const float* cell_anchors, int A, int B,
+                                   int Hf, int Wf, int stride, const int32_t* image_sizes, float* props,
+                                   float* scores, int32_t* flags, float wx, float wy, float ww, float wh,
+                                   void* stream) {
+  return sfod_rpn_decode_shift(rpn_out, ld, cell_anchors, A, B, Hf, Wf, stride, image_sizes, props, scores, flags,
+                               wx, wy, ww, wh, 0.f, stream);
 }
 
 extern "C" int sfod_rpn_decode(const float* rpn_out, int ld, const float* cell_anchors, int A, int B,
@@ -219,7 +237,7 @@ extern "C" int sfod_rpn_decode(const float* rpn_out, int ld, const float* cell_a
 }
 
 __global__ void k_rpn_gather_topk(const float* __restrict__ props, const float* __restrict__ sscores,
-                                  const int32_t* __restrict__ sidx, int NA, int k,
+                                  const int32_t* __restrict__ sidx, int NA, int k, float min_size,
                                   float* __restrict__ cboxes, float* __restrict__ cscores,
                                   uint8_t* __restrict__ cvalid) {
   const int b = blockIdx.y;
@@ -229,19 +247,30 @@ __global__ void k_rpn_gather_topk(const float* __restrict__ props, const float* 
   Box bx = load_box(props + ((int64_t)b * NA + idx) * 4);
   store_box(cboxes + ((int64_t)b * k + j) * 4, bx);
   cscores[(int64_t)b * k + j] = sscores[(int64_t)b * NA + j];
-  // Boxes.nonempty(threshold=0): strict
-  cvalid[(int64_t)b * k + j] = ((bx.x2 - bx.x1) > 0.f && (bx.y2 - bx.y1) > 0.f) ? 1 : 0;
+  // Boxes.nonempty(threshold=min_size): strict
+  cvalid[(int64_t)b * k + j] = ((bx.x2 - bx.x1) > min_size && (bx.y2 - bx.y1) > min_size) ? 1 : 0;
+}
+
+extern "C" int sfod_rpn_gather_topk_opt(const float* props, const float* sorted_scores,
+                                        const int32_t* sorted_idx, int B, int NA, int k, float min_size,
+                                        float* cand_boxes, float* cand_scores, uint8_t* cand_valid, void* stream) {
+  SFOD_REQUIRE_EXTENTS("rpn_gather_topk", B, NA, k);
+  SFOD_REQUIRE(k <= NA, "k > NA");
+  SFOD_REQUIRE(isfinite(min_size) && min_size >= 0.f, "rpn_gather_topk: min_size must be finite and >= 0");
+  SFOD_REQUIRE(sfod_prod_fits({B, NA, 4}, 1LL << 40), "rpn_gather_topk: oversized problem");
+  SFOD_REQUIRE(B == 0 || k == 0 || (props && sorted_scores && sorted_idx && cand_boxes && cand_scores && cand_valid),
+               "rpn_gather_topk: null argument");
+  dim3 grid(cdiv(k, 256), B);
+  hipLaunchKernelGGL(k_rpn_gather_topk, grid, dim3(256), 0, (hipStream_t)stream, props, sorted_scores,
+                     sorted_idx, NA, k, min_size, cand_boxes, cand_scores, cand_valid);
+  return sfod_check_launch("rpn_gather_topk");
 }
 
 extern "C" int sfod_rpn_gather_topk(const float* props, const float* sorted_scores,
                                     const int32_t* sorted_idx, int B, int NA, int k, float* cand_boxes,
                                     float* cand_scores, uint8_t* cand_valid, void* stream) {
-  SFOD_REQUIRE_EXTENTS("rpn_gather_topk", B, NA, k);
-  SFOD_REQUIRE(k <= NA, "k > NA");
-  dim3 grid(cdiv(k, 256), B);
-  hipLaunchKernelGGL(k_rpn_gather_topk, grid, dim3(256), 0, (hipStream_t)stream, props, sorted_scores,
-                     sorted_idx, NA, k, cand_boxes, cand_scores, cand_valid);
-  return sfod_check_launch("rpn_gather_topk");
+  return sfod_rpn_gather_topk_opt(props, sorted_scores, sorted_idx, B, NA, k, 0.f, cand_boxes, cand_scores, cand_valid,
+                                  stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -649,7 +678,7 @@ extern "C" int sfod_gather_kept(const float* cand_boxes, const float* cand_score
 #define GT_MAX 256
 
 __global__ void __launch_bounds__(256)
-k_anchor_match_a(const float* __restrict__ cell, int A, int Hf, int Wf, int stride,
+k_anchor_match_a(const float* __restrict__ cell, int A, int Hf, int Wf, int stride, float shift,
                  const float* __restrict__ gt, const int32_t* __restrict__ gt_count, int Gcap,
                  float* __restrict__ best_val, int32_t* __restrict__ matched, float* gtmax) {
   __shared__ float sgt[GT_MAX * 4];
@@ -660,7 +689,7 @@ k_anchor_match_a(const float* __restrict__ cell, int A, int Hf, int Wf, int stri
   __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool act = i < NA;
-  Box anc = anchor_at(cell, A, Wf, stride, act ? i : 0);
+  Box anc = anchor_at(cell, A, Wf, stride, shift, act ? i : 0);
   float best = -1.f;
   int arg = 0;
   for (int g = 0; g < G; ++g) {
@@ -678,10 +707,10 @@ k_anchor_match_a(const float* __restrict__ cell, int A, int Hf, int Wf, int stri
 }
 
 __global__ void __launch_bounds__(256)
-k_anchor_match_b(const float* __restrict__ cell, int A, int Hf, int Wf, int stride,
+k_anchor_match_b(const float* __restrict__ cell, int A, int Hf, int Wf, int stride, float shift,
                  const float* __restrict__ gt, const int32_t* __restrict__ gt_count, int Gcap, float lo,
                  float hi, const float* __restrict__ best_val, const float* __restrict__ gtmax,
-                 int8_t* __restrict__ labels) {
+                 float bthr, const int32_t* __restrict__ sizes, int8_t* __restrict__ labels) {
   __shared__ float sgt[GT_MAX * 4];
   __shared__ float smax[GT_MAX];
   const int b = blockIdx.y;
@@ -692,23 +721,36 @@ k_anchor_match_b(const float* __restrict__ cell, int A, int Hf, int Wf, int stri
   __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= NA) return;
-  if (G == 0) { labels[(int64_t)b * NA + i] = 0; return; }
-  const float best = best_val[(int64_t)b * NA + i];
-  int8_t lab = (best < lo) ? 0 : ((best < hi) ? -1 : 1);
-  Box anc = anchor_at(cell, A, Wf, stride, i);
-  bool lowq = false;
-  for (int g = 0; g < G; ++g) {
-    Box gb = Box{sgt[g * 4], sgt[g * 4 + 1], sgt[g * 4 + 2], sgt[g * 4 + 3]};
-    lowq = lowq || (iou_pairwise(gb, anc) == smax[g]);
+  Box anc = anchor_at(cell, A, Wf, stride, shift, i);
+  int8_t lab = 0;                               // no ground truth: d2's Matcher on an empty matrix labels everything 0
+  if (G > 0) {
+    const float best = best_val[(int64_t)b * NA + i];
+    lab = (best < lo) ? 0 : ((best < hi) ? -1 : 1);
+    bool lowq = false;
+    for (int g = 0; g < G; ++g) {
+      Box gb = Box{sgt[g * 4], sgt[g * 4 + 1], sgt[g * 4 + 2], sgt[g * 4 + 3]};
+      lowq = lowq || (iou_pairwise(gb, anc) == smax[g]);
+    }
+    if (lowq) lab = 1;
   }
-  if (lowq) lab = 1;
+  // MODEL.RPN.BOUNDARY_THRESH (bthr >= 0): Boxes.inside_box on the anchor, after the matcher's label; outside -> ignored
+  if (bthr >= 0.f) {
+    const float h = (float)sizes[b * 2 + 0], w = (float)sizes[b * 2 + 1];
+    const bool inside = anc.x1 >= -bthr && anc.y1 >= -bthr && anc.x2 < w + bthr && anc.y2 < h + bthr;
+    if (!inside) lab = -1;
+  }
   labels[(int64_t)b * NA + i] = lab;
 }
 
-extern "C" int sfod_anchor_match(const float* cell_anchors, int A, int B, int Hf, int Wf, int stride,
-                                 const float* gt_boxes, const int32_t* gt_count, int Gcap, float lo,
-                                 float hi, int32_t* matched, int8_t* labels, float* gtmax, void* stream) {
+extern "C" int sfod_anchor_match_opt(const float* cell_anchors, int A, int B, int Hf, int Wf, int stride,
+                                     const float* gt_boxes, const int32_t* gt_count, int Gcap, float lo,
+                                     float hi, float shift, float boundary_thresh, const int32_t* image_sizes,
+                                     int32_t* matched, int8_t* labels, float* gtmax, void* stream) {
   SFOD_REQUIRE_EXTENTS("anchor_match", A, B, Hf, Wf, stride, Gcap);
+  SFOD_REQUIRE(sfod_anchor_shift_ok(shift, stride), "anchor_match: anchor shift must be finite and in [0, stride)");
+  SFOD_REQUIRE(!isnan(boundary_thresh) && boundary_thresh < INFINITY,
+               "anchor_match: boundary_thresh must be a finite value >= 0, or negative (off)");
+  SFOD_REQUIRE(boundary_thresh < 0.f || image_sizes, "anchor_match: boundary_thresh >= 0 needs image_sizes");
   SFOD_REQUIRE(sfod_prod_fits({Hf, Wf, A}) && sfod_prod_fits({B, Hf, Wf, A}, 1LL << 40) && sfod_prod_fits({B, Gcap}),
                "anchor_match: oversized anchor grid");
   SFOD_REQUIRE(cell_anchors && gt_boxes && gt_count && matched && labels && gtmax, "anchor_match: null argument");
@@ -719,19 +761,27 @@ extern "C" int sfod_anchor_match(const float* cell_anchors, int A, int B, int Hf
   float* best_val = gtmax + (int64_t)B * Gcap;
   (void)hipMemsetAsync(gtmax, 0, sizeof(float) * B * Gcap, s);
   dim3 grid(cdiv(NA, 256), B);
-  hipLaunchKernelGGL(k_anchor_match_a, grid, dim3(256), 0, s, cell_anchors, A, Hf, Wf, stride, gt_boxes,
+  hipLaunchKernelGGL(k_anchor_match_a, grid, dim3(256), 0, s, cell_anchors, A, Hf, Wf, stride, shift, gt_boxes,
                      gt_count, Gcap, best_val, matched, gtmax);
   int rc = sfod_check_launch("anchor_match_a");
   if (rc) return rc;
-  hipLaunchKernelGGL(k_anchor_match_b, grid, dim3(256), 0, s, cell_anchors, A, Hf, Wf, stride, gt_boxes,
-                     gt_count, Gcap, lo, hi, best_val, gtmax, labels);
+  hipLaunchKernelGGL(k_anchor_match_b, grid, dim3(256), 0, s, cell_anchors, A, Hf, Wf, stride, shift, gt_boxes,
+                     gt_count, Gcap, lo, hi, best_val, gtmax, boundary_thresh < 0.f ? -1.f : boundary_thresh, image_sizes,
+                     labels);
   return sfod_check_launch("anchor_match_b");
+}
+
+extern "C" int sfod_anchor_match(const float* cell_anchors, int A, int B, int Hf, int Wf, int stride,
+                                 const float* gt_boxes, const int32_t* gt_count, int Gcap, float lo,
+                                 float hi, int32_t* matched, int8_t* labels, float* gtmax, void* stream) {
+  return sfod_anchor_match_opt(cell_anchors, A, B, Hf, Wf, stride, gt_boxes, gt_count, Gcap, lo, hi, 0.f, -1.f, nullptr,
+                               matched, labels, gtmax, stream);
 }
 
 __global__ void __launch_bounds__(256)
 k_roi_match(const float* __restrict__ boxes, const int32_t* __restrict__ box_count, int P,
             const float* __restrict__ gt, const int32_t* __restrict__ gt_classes,
-            const int32_t* __restrict__ gt_count, int Gcap, float thr, int K,
+            const int32_t* __restrict__ gt_count, int Gcap, float lo, float hi, int K,
             int32_t* __restrict__ matched, int32_t* __restrict__ cls) {
   __shared__ float sgt[GT_MAX * 4];
   const int b = blockIdx.y;
@@ -752,19 +802,33 @@ k_roi_match(const float* __restrict__ boxes, const int32_t* __restrict__ box_cou
     if (v > best) { best = v; arg = g; }
   }
   matched[o] = arg;
-  cls[o] = (best >= thr) ? gt_classes[(int64_t)b * Gcap + arg] : K;
+  // Matcher [lo, hi] / [0, -1, 1] then _sample_proposals: foreground class, -1 (ignored, never sampled), K (background);
+  // lo == hi is the one-threshold form [t] / [0, 1]
+  cls[o] = (best >= hi) ? gt_classes[(int64_t)b * Gcap + arg] : ((best >= lo) ? -1 : K);
+}
+
+extern "C" int sfod_roi_match_opt(const float* boxes, const int32_t* box_count, int B, int P,
+                                  const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_count,
+                                  int Gcap, float lo, float hi, int num_classes, int32_t* matched, int32_t* cls,
+                                  void* stream) {
+  SFOD_REQUIRE_EXTENTS("roi_match", B, P, Gcap, num_classes);
+  SFOD_REQUIRE(Gcap <= GT_MAX, "Gcap > 256");
+  SFOD_REQUIRE(isfinite(lo) && isfinite(hi) && lo <= hi, "roi_match: thresholds must be finite with lo <= hi");
+  SFOD_REQUIRE(sfod_prod_fits({B, P, 4}, 1LL << 40) && sfod_prod_fits({B, Gcap, 4}), "roi_match: oversized problem");
+  SFOD_REQUIRE(B == 0 || P == 0 || (boxes && box_count && gt_count && matched && cls && (Gcap == 0 || (gt_boxes && gt_classes))),
+               "roi_match: null argument");
+  dim3 grid(cdiv(P, 256), B);
+  hipLaunchKernelGGL(k_roi_match, grid, dim3(256), 0, (hipStream_t)stream, boxes, box_count, P, gt_boxes,
+                     gt_classes, gt_count, Gcap, lo, hi, num_classes, matched, cls);
+  return sfod_check_launch("roi_match");
 }
 
 extern "C" int sfod_roi_match(const float* boxes, const int32_t* box_count, int B, int P,
                               const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_count,
                               int Gcap, float thr, int num_classes, int32_t* matched, int32_t* cls,
                               void* stream) {
-  SFOD_REQUIRE_EXTENTS("roi_match", B, P, Gcap, num_classes);
-  SFOD_REQUIRE(Gcap <= GT_MAX, "Gcap > 256");
-  dim3 grid(cdiv(P, 256), B);
-  hipLaunchKernelGGL(k_roi_match, grid, dim3(256), 0, (hipStream_t)stream, boxes, box_count, P, gt_boxes,
-                     gt_classes, gt_count, Gcap, thr, num_classes, matched, cls);
-  return sfod_check_launch("roi_match");
+  return sfod_roi_match_opt(boxes, box_count, B, P, gt_boxes, gt_classes, gt_count, Gcap, thr, thr, num_classes, matched,
+                            cls, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -985,7 +1049,7 @@ k_rpn_loss(const float* __restrict__ rpn_out, int ld, const float* __restrict__ 
            int Wf, int stride, const int8_t* __restrict__ labels, const int32_t* __restrict__ matched,
            const float* __restrict__ gt, const int32_t* __restrict__ gt_count, int Gcap, float inv_norm,
            const float* __restrict__ grad_scale, float* __restrict__ d_out, float* __restrict__ partial,
-           BoxWeights bw, int loss_type, float beta) {
+           BoxWeights bw, int loss_type, float beta, float shift) {
   __shared__ float red[4];
   const int b = blockIdx.y;
   const int NA = Hf * Wf * A;
@@ -1010,7 +1074,7 @@ k_rpn_loss(const float* __restrict__ rpn_out, int ld, const float* __restrict__ 
       const int G = min(gt_count[b], Gcap);
       Box t{0.f, 0.f, 0.f, 0.f};
       if (G > 0) t = load_box(gt + ((int64_t)b * Gcap + matched[(int64_t)b * NA + i]) * 4);
-      Box anc = anchor_at(cell, A, Wf, stride, i);
+      Box anc = anchor_at(cell, A, Wf, stride, shift, i);
       float d[4], g[4];
       for (int j = 0; j < 4; ++j) d[j] = rpn_out[rowoff + A + a * 4 + j];
       lloc += box_reg_term(anc, t, d, bw, loss_type, beta, grad_scale ? g : nullptr);
@@ -1047,12 +1111,14 @@ k_sum_partials2(const float* __restrict__ partial, int nblk, float scale0, float
   }
 }
 
-extern "C" int sfod_rpn_loss_opt(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
-                                 int Wf, int stride, const int8_t* labels, const int32_t* matched,
-                                 const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
-                                 float* loss, const float* grad_scale, float* d_rpn_out, float* ws, float wx,
-                                 float wy, float ww, float wh, int loss_type, float beta, void* stream) {
+extern "C" int sfod_rpn_loss_shift(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
+                                   int Wf, int stride, const int8_t* labels, const int32_t* matched,
+                                   const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
+                                   float* loss, const float* grad_scale, float* d_rpn_out, float* ws, float wx,
+                                   float wy, float ww, float wh, int loss_type, float beta, float shift,
+                                   void* stream) {
   SFOD_REQUIRE_EXTENTS("rpn_loss", ld, A, B, Hf, Wf, stride, Gcap, batch_per_image);
+  SFOD_REQUIRE(sfod_anchor_shift_ok(shift, stride), "rpn_loss: anchor shift must be finite and in [0, stride)");
   SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "rpn_loss: box weights must be finite and > 0");
   SFOD_REQUIRE(loss_type == BOXREG_SMOOTH_L1 || loss_type == BOXREG_GIOU, "rpn_loss: loss_type must be 0 (smooth_l1) or 1 (giou)");
   SFOD_REQUIRE(beta >= 0.f && isfinite(beta), "rpn_loss: beta must be finite and >= 0");
@@ -1070,12 +1136,22 @@ extern "C" int sfod_rpn_loss_opt(const float* rpn_out, int ld, const float* cell
   dim3 grid(cdiv(NA, 256), B);
   hipLaunchKernelGGL(k_rpn_loss, grid, dim3(256), 0, s, rpn_out, ld, cell_anchors, A, Hf, Wf, stride,
                      labels, matched, gt_boxes, gt_count, Gcap, inv_norm, grad_scale, d_rpn_out, ws,
-                     BoxWeights{wx, wy, ww, wh}, loss_type, beta);
+                     BoxWeights{wx, wy, ww, wh}, loss_type, beta, shift);
   int rc = sfod_check_launch("rpn_loss");
   if (rc) return rc;
   hipLaunchKernelGGL(k_sum_partials2, dim3(1), dim3(256), 0, s, ws, (int)(grid.x * grid.y), inv_norm,
                      inv_norm, (const int32_t*)nullptr, loss);
   return sfod_check_launch("rpn_loss_sum");
+}
+
+extern "C" int sfod_rpn_loss_opt(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,
+                                 int Wf, int stride, const int8_t* labels, const int32_t* matched,
+                                 const float* gt_boxes, const int32_t* gt_count, int Gcap, int batch_per_image,
+                                 float* loss, const float* grad_scale, float* d_rpn_out, float* ws, float wx,
+                                 float wy, float ww, float wh, int loss_type, float beta, void* stream) {
+  return sfod_rpn_loss_shift(rpn_out, ld, cell_anchors, A, B, Hf, Wf, stride, labels, matched, gt_boxes, gt_count, Gcap,
+                             batch_per_image, loss, grad_scale, d_rpn_out, ws, wx, wy, ww, wh, loss_type, beta, 0.f,
+                             stream);
 }
 
 extern "C" int sfod_rpn_loss(const float* rpn_out, int ld, const float* cell_anchors, int A, int B, int Hf,

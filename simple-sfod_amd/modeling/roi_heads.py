@@ -22,6 +22,7 @@ from ..structures import Boxes, Instances, ShapeSpec
 from .offchain import OffChain as _OffChain, heads_on as _heads_on
 from .batched import BatchedDetections, BatchedGT, BatchedProposals
 from .box_regression import ROI_DEFAULT_WEIGHTS, roi_box_reg_options
+from .proposal_options import roi_iou_band
 from .roi_pooler import roi_pooler_options
 
 
@@ -263,8 +264,10 @@ class StandardROIHeads(nn.Module):
         self.batch_size_per_image = r.BATCH_SIZE_PER_IMAGE
         self.positive_fraction = r.POSITIVE_FRACTION
         self.proposal_append_gt = r.PROPOSAL_APPEND_GT
-        assert list(r.IOU_THRESHOLDS) == [r.IOU_THRESHOLDS[0]] and list(r.IOU_LABELS) == [0, 1]
-        self.iou_threshold = r.IOU_THRESHOLDS[0]
+        # [t] / [0, 1], or an ignore band [lo, hi] / [0, -1, 1] (anything else: ValueError naming the keys).  ``_iou_lo`` is
+        # what ``native.roi_match`` takes: None = the one-threshold entry point, as before the band was built
+        lo, self.iou_threshold = roi_iou_band(cfg)
+        self._iou_lo = None if lo == self.iou_threshold else lo
         self.box_in_features = self.in_features = r.IN_FEATURES
         assert len(self.in_features) == 1
         shape = input_shape[self.in_features[0]]
@@ -412,7 +415,8 @@ class StandardROIHeads(nn.Module):
         else:
             boxes, count = props.boxes, props.count
         matched, cls = native.roi_match(boxes, count, targets.boxes, targets.classes, targets.count,
-                                        self.iou_threshold, self.num_classes)
+                                        self.iou_threshold, self.num_classes,
+                                        **({"lo": self._iou_lo} if self._iou_lo is not None else {}))
         keys = keys if keys is not None else getattr(self, "_forced_keys", None)
         if keys is None:
             keys = torch.randint(0, 2 ** 31 - 1, (B, boxes.shape[1]), dtype=torch.int32, device=boxes.device)

@@ -19,6 +19,7 @@ from ..registry import PROPOSAL_GENERATOR_REGISTRY
 from .batched import BatchedGT, BatchedProposals
 from .box_regression import RPN_DEFAULT_WEIGHTS, rpn_box_reg_options
 from .offchain import OffChain, heads_on, take_loss_grads_ready
+from .proposal_options import proposal_options
 
 
 class BufferList(nn.Module):
@@ -35,8 +36,8 @@ class BufferList(nn.Module):
 
 
 class DefaultAnchorGenerator(nn.Module):
-    """d2 DefaultAnchorGenerator, offset 0.0 (A.3).  Only the cell anchors are materialised: the
-    grid shift of an anchor index is recomputed in-register by the kernels."""
+    """d2 DefaultAnchorGenerator (A.3).  Only the cell anchors are materialised: the grid shift of an anchor index --
+    ``float32(OFFSET * stride) + x * stride`` -- is recomputed in-register by the kernels."""
     box_dim = 4
 
     def __init__(self, cfg, input_shape):
@@ -45,6 +46,7 @@ class DefaultAnchorGenerator(nn.Module):
         ratios = cfg.MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS
         assert len(input_shape) == 1, "single-level RPN only (C4-style heads)"
         self.strides = [s.stride for s in input_shape]
+        self.offset = proposal_options(cfg).offset          # MODEL.ANCHOR_GENERATOR.OFFSET, in [0, 1)
         self.cell_anchors = BufferList([self.generate_cell_anchors(sizes[0], ratios[0])])
 
     @staticmethod
@@ -67,8 +69,10 @@ class DefaultAnchorGenerator(nn.Module):
         out = []
         for f, stride, cell in zip(features, self.strides, self.cell_anchors):
             hf, wf = f.shape[-2:]
-            sx = torch.arange(0, wf * stride, step=stride, dtype=torch.float32, device=cell.device)
-            sy = torch.arange(0, hf * stride, step=stride, dtype=torch.float32, device=cell.device)
+            # d2 _create_grid_offsets: float32(offset * stride) + x * stride, one fp32 add (what the kernels compute)
+            shift = torch.tensor(self.offset * stride, dtype=torch.float32, device=cell.device)
+            sx = shift + torch.arange(0, wf * stride, step=stride, dtype=torch.float32, device=cell.device)
+            sy = shift + torch.arange(0, hf * stride, step=stride, dtype=torch.float32, device=cell.device)
             yy, xx = torch.meshgrid(sy, sx, indexing="ij")
             shifts = torch.stack((xx.reshape(-1), yy.reshape(-1), xx.reshape(-1), yy.reshape(-1)), dim=1)
             out.append((shifts.view(-1, 1, 4) + cell.view(1, -1, 4)).reshape(-1, 4))
@@ -102,7 +106,8 @@ class _RPNLossFn(torch.autograd.Function):
         pf = rpn._take_prefetched(feat_nchw)        # the head's forward may have run already (``prefetch``): same state
         st = pf[0] if pf is not None else rpn._head_forward(feat_nchw, need_grad=True)
         rpn._prefetched_proposals = pf[1] if pf is not None else None
-        loss, lab_state = rpn._loss_forward(st, gt, keys)
+        sizes = rpn.__dict__.pop("_loss_image_sizes", None)     # set by ``RPN.forward`` for the boundary test
+        loss, lab_state = rpn._loss_forward(st, gt, keys, **({"image_sizes": sizes} if sizes is not None else {}))
         ctx.rpn, ctx.st, ctx.lab_state, ctx.gt, ctx.weights = rpn, st, lab_state, gt, weights
         rpn._last_head_state = st
         return loss[0] * weights[0], loss[1] * weights[1]
@@ -149,6 +154,11 @@ class RPN(nn.Module):
         self.box_reg_loss_type, self.smooth_l1_beta = self.box_reg.loss_type, self.box_reg.beta
         self.box_reg_weights = self.box_reg.weights
         self._box_reg = None if self.box_reg.is_default(RPN_DEFAULT_WEIGHTS) else self.box_reg
+        # ANCHOR_GENERATOR.OFFSET / RPN.BOUNDARY_THRESH / PROPOSAL_GENERATOR.MIN_SIZE (and a ValueError naming the key for
+        # RPN.HEAD_NAME / RPN.CONV_DIMS / ANCHOR_GENERATOR.NAME values that are not built).  ``_shift`` etc. are what the native
+        # calls take; at the defaults (0, -1, 0) the wrappers make the calls they made before these keys were read
+        self.proposal_options = po = proposal_options(cfg)
+        self._shift, self._boundary_thresh, self._min_size = po.shift(self.stride), po.boundary_thresh, po.min_size
         self.pre_nms_topk = {True: r.PRE_NMS_TOPK_TRAIN, False: r.PRE_NMS_TOPK_TEST}
         self.post_nms_topk = {True: r.POST_NMS_TOPK_TRAIN, False: r.POST_NMS_TOPK_TEST}
         self.nms_thresh = r.NMS_THRESH
@@ -214,11 +224,11 @@ class RPN(nn.Module):
         if sizes_dev is None:
             sizes_dev = self._sizes_dev(image_sizes, dev)
         props, scores = native.rpn_decode(st["rpn_out"], self._cell(), B, Hf, Wf, self.stride, sizes_dev, self._flags,
-                                          box_reg=self._box_reg)
+                                          box_reg=self._box_reg, **self._shift_kw())
         ss, si = native.segmented_sort_desc(scores)
         NA = scores.shape[1]
         k = min(self.pre_nms_topk[self.training], NA)
-        cb, cs, cv = native.rpn_gather_topk(props, ss, si, k)
+        cb, cs, cv = native.rpn_gather_topk(props, ss, si, k, **({"min_size": self._min_size} if self._min_size else {}))
         post = self.post_nms_topk[self.training]
         keep_idx, keep_cnt = native.nms(cb, self.nms_thresh, post, valid=cv)
         pb, ps = native.gather_kept(cb, cs, keep_idx, keep_cnt)
@@ -231,14 +241,24 @@ class RPN(nn.Module):
             raise FloatingPointError("Predicted boxes or scores contain Inf/NaN. Training has diverged.")
 
     # ---- losses --------------------------------------------------------------------------------------
-    def _loss_forward(self, st, gt, keys):
+    def _shift_kw(self):
+        """keyword arguments of the anchor-building native calls: none at OFFSET 0 (the calls as they were)"""
+        return {"shift": self._shift} if self._shift else {}
+
+    def _loss_forward(self, st, gt, keys, image_sizes=None):
+        """``image_sizes``: [(h, w)] of the batch, read by the boundary test only (MODEL.RPN.BOUNDARY_THRESH >= 0)"""
         B, Hf, Wf = st["shape"]
         cell = self._cell()
         lo, hi = self.iou_thresholds
-        matched, labels = native.anchor_match(cell, B, Hf, Wf, self.stride, gt.boxes, gt.count, lo, hi)
+        kw = self._shift_kw()
+        if self._boundary_thresh >= 0:
+            if image_sizes is None:
+                raise ValueError("MODEL.RPN.BOUNDARY_THRESH >= 0 needs the image sizes of the batch")
+            kw.update(boundary_thresh=self._boundary_thresh, sizes=self._sizes_dev(image_sizes, st["rpn_out"].device))
+        matched, labels = native.anchor_match(cell, B, Hf, Wf, self.stride, gt.boxes, gt.count, lo, hi, **kw)
         native.subsample_rpn_(labels, keys, self.batch_size_per_image, self.positive_fraction)
         loss, _ = native.rpn_loss(st["rpn_out"], cell, B, Hf, Wf, self.stride, labels, matched, gt.boxes,
-                                  gt.count, self.batch_size_per_image, box_reg=self._box_reg)
+                                  gt.count, self.batch_size_per_image, box_reg=self._box_reg, **self._shift_kw())
         return loss, (labels, matched)
 
     def _loss_backward(self, st, lab_state, gt, grad_scale):
@@ -249,7 +269,8 @@ class RPN(nn.Module):
         dtype = native.grad_dtype_of(self.compute_dtype)      # operands of the backward products ("f16x3": bf16 pairs)
         dt = native.dt_of_dtype(dtype)
         _, d_out = native.rpn_loss(st["rpn_out"], cell, B, Hf, Wf, self.stride, labels, matched, gt.boxes,
-                                   gt.count, self.batch_size_per_image, grad_scale=grad_scale, box_reg=self._box_reg)
+                                   gt.count, self.batch_size_per_image, grad_scale=grad_scale, box_reg=self._box_reg,
+                                   **self._shift_kw())
         M = B * Hf * Wf
         t2 = st["t"].view(M, C)
         d_out_c = native.cast(d_out, dtype)
@@ -291,6 +312,8 @@ class RPN(nn.Module):
             # losses() applies loss_weight, PseudoLabRPN.forward applies it again (rpn.py:49)
             twice = isinstance(self, PseudoLabRPN)
             wts = (self.loss_weight["loss_rpn_cls"] ** (2 if twice else 1), self.loss_weight["loss_rpn_loc"] ** (2 if twice else 1))
+            if self._boundary_thresh >= 0:
+                self._loss_image_sizes = list(images.image_sizes)
             l_cls, l_loc = _RPNLossFn.apply(self, feat, gt, keys, wts, *self.rpn_head.params())
             st = self._last_head_state
             losses = {"loss_rpn_cls": l_cls, "loss_rpn_loc": l_loc}

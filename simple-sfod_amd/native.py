@@ -1153,12 +1153,20 @@ class BoxRegOptions:
         return f"BoxRegOptions({self.weights}, {self.loss_type!r}, beta={self.beta}, cls_agnostic={self.cls_agnostic})"
 
 
-def rpn_decode(rpn_out, cell, B, Hf, Wf, stride, sizes, flags, box_reg=None):
+_RPN_UNIT_WEIGHTS = (1.0, 1.0, 1.0, 1.0)
+
+
+def rpn_decode(rpn_out, cell, B, Hf, Wf, stride, sizes, flags, box_reg=None, shift=0.0):
+    """``shift`` (here, in ``anchor_match`` and in ``rpn_loss``): MODEL.ANCHOR_GENERATOR.OFFSET * stride as the product of two python
+    doubles; ctypes rounds it to float32 once at the call (include/sfod_hip.h)"""
     A = cell.shape[0]
     NA = Hf * Wf * A
     props = torch.empty(B, NA, 4, dtype=torch.float32, device=rpn_out.device)
     scores = torch.empty(B, NA, dtype=torch.float32, device=rpn_out.device)
-    if box_reg is None:
+    if shift != 0.0:
+        call("sfod_rpn_decode_shift", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, sizes, props, scores, flags,
+             *(box_reg.weights if box_reg is not None else _RPN_UNIT_WEIGHTS), float(shift))
+    elif box_reg is None:
         call("sfod_rpn_decode", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, sizes, props, scores, flags)
     else:
         call("sfod_rpn_decode_opt", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, sizes, props, scores, flags,
@@ -1186,13 +1194,17 @@ def segmented_sort_desc(keys):
     return out_keys, out_idx
 
 
-def rpn_gather_topk(props, sorted_scores, sorted_idx, k):
+def rpn_gather_topk(props, sorted_scores, sorted_idx, k, min_size=0.0):
+    """``min_size``: MODEL.PROPOSAL_GENERATOR.MIN_SIZE -- valid = wider AND taller than it, strict"""
     B, NA, _ = props.shape
     dev = props.device
     cb = torch.empty(B, k, 4, dtype=torch.float32, device=dev)
     cs = torch.empty(B, k, dtype=torch.float32, device=dev)
     cv = torch.empty(B, k, dtype=torch.uint8, device=dev)
-    call("sfod_rpn_gather_topk", props, sorted_scores, sorted_idx, B, NA, k, cb, cs, cv)
+    if min_size == 0.0:
+        call("sfod_rpn_gather_topk", props, sorted_scores, sorted_idx, B, NA, k, cb, cs, cv)
+    else:
+        call("sfod_rpn_gather_topk_opt", props, sorted_scores, sorted_idx, B, NA, k, float(min_size), cb, cs, cv)
     return cb, cs, cv
 
 
@@ -1224,7 +1236,9 @@ def gather_kept(cand_boxes, cand_scores, keep_idx, keep_count):
     return ob, os_
 
 
-def anchor_match(cell, B, Hf, Wf, stride, gt_boxes, gt_count, lo, hi):
+def anchor_match(cell, B, Hf, Wf, stride, gt_boxes, gt_count, lo, hi, shift=0.0, boundary_thresh=-1.0, sizes=None):
+    """``boundary_thresh`` >= 0 (MODEL.RPN.BOUNDARY_THRESH): anchors not inside the image grown by it get label -1; it needs
+    ``sizes``, int32 [B, 2] as (h, w) on the device"""
     A = cell.shape[0]
     NA = Hf * Wf * A
     dev = gt_boxes.device
@@ -1232,17 +1246,27 @@ def anchor_match(cell, B, Hf, Wf, stride, gt_boxes, gt_count, lo, hi):
     matched = torch.empty(B, NA, dtype=torch.int32, device=dev)
     labels = torch.empty(B, NA, dtype=torch.int8, device=dev)
     scratch = torch.empty(B * gcap + B * NA, dtype=torch.float32, device=dev)
-    call("sfod_anchor_match", cell, A, B, Hf, Wf, stride, gt_boxes, gt_count, gcap, float(lo), float(hi),
-         matched, labels, scratch)
+    if shift == 0.0 and boundary_thresh < 0:
+        call("sfod_anchor_match", cell, A, B, Hf, Wf, stride, gt_boxes, gt_count, gcap, float(lo), float(hi),
+             matched, labels, scratch)
+    else:
+        call("sfod_anchor_match_opt", cell, A, B, Hf, Wf, stride, gt_boxes, gt_count, gcap, float(lo), float(hi),
+             float(shift), float(boundary_thresh), sizes if boundary_thresh >= 0 else None, matched, labels, scratch)
     return matched, labels
 
 
-def roi_match(boxes, box_count, gt_boxes, gt_classes, gt_count, thr, num_classes):
+def roi_match(boxes, box_count, gt_boxes, gt_classes, gt_count, thr, num_classes, lo=None):
+    """``lo``: lower end of an ignore band [lo, thr) (MODEL.ROI_HEADS.IOU_THRESHOLDS [lo, thr] / IOU_LABELS [0, -1, 1]): ROIs
+    whose best IoU falls in it get class -1 and are never sampled.  None: the one-threshold form [thr] / [0, 1]."""
     B, P, _ = boxes.shape
     matched = torch.empty(B, P, dtype=torch.int32, device=boxes.device)
     cls = torch.empty(B, P, dtype=torch.int32, device=boxes.device)
-    call("sfod_roi_match", boxes, box_count, B, P, gt_boxes, gt_classes, gt_count, gt_boxes.shape[1],
-         float(thr), num_classes, matched, cls)
+    if lo is None:
+        call("sfod_roi_match", boxes, box_count, B, P, gt_boxes, gt_classes, gt_count, gt_boxes.shape[1],
+             float(thr), num_classes, matched, cls)
+    else:
+        call("sfod_roi_match_opt", boxes, box_count, B, P, gt_boxes, gt_classes, gt_count, gt_boxes.shape[1],
+             float(lo), float(thr), num_classes, matched, cls)
     return matched, cls
 
 
@@ -1262,7 +1286,7 @@ def subsample_roi(cls, keys, num, pos_frac, bg_label):
 
 
 def rpn_loss(rpn_out, cell, B, Hf, Wf, stride, labels, matched, gt_boxes, gt_count, batch_per_image,
-             grad_scale=None, box_reg=None):
+             grad_scale=None, box_reg=None, shift=0.0):
     A = cell.shape[0]
     NA = Hf * Wf * A
     dev = rpn_out.device
@@ -1270,7 +1294,12 @@ def rpn_loss(rpn_out, cell, B, Hf, Wf, stride, labels, matched, gt_boxes, gt_cou
     nblk = (NA + 255) // 256 * B
     ws = torch.empty(nblk * 2, dtype=torch.float32, device=dev)
     d_out = torch.empty_like(rpn_out) if grad_scale is not None else None
-    if box_reg is None:
+    if shift != 0.0:
+        br = box_reg if box_reg is not None else BoxRegOptions(_RPN_UNIT_WEIGHTS)
+        call("sfod_rpn_loss_shift", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, labels, matched, gt_boxes,
+             gt_count, gt_boxes.shape[1], batch_per_image, loss, grad_scale, d_out, ws, *br.weights,
+             BOX_REG_LOSS_TYPES[br.loss_type], br.beta, float(shift))
+    elif box_reg is None:
         call("sfod_rpn_loss", rpn_out, rpn_out.shape[-1], cell, A, B, Hf, Wf, stride, labels, matched, gt_boxes,
              gt_count, gt_boxes.shape[1], batch_per_image, loss, grad_scale, d_out, ws)
     else:
