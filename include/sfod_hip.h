@@ -640,6 +640,26 @@ int sfod_bpc_loss_opt(const float* pred, int ld, int R, int K, const float* rois
                       const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws, float wx, float wy,
                       float ww, float wh, int cls_agnostic, void* stream);
 
+/* F1Evaluator (daod/evaluation/f1_evaluator.py:8-230, appended to every trainer's evaluator list, base.py:149): per image
+ * and class the counts TP / FP / FN that its F1 score is made of, one wavefront per image, nothing read back.
+ *   1. detector_postprocess to the loader's scale: box * (sx, sy, sx, sy) in fp32, clip to [0, w] x [0, h], keep width > 0
+ *      and height > 0;  2. keep score >= `score` (fp32);  3. keep the `top_n` highest scores over all classes together
+ *      (equal scores: the later index ranks first);  4. detection coordinates truncated toward zero to integers, ground
+ *      truth stays fp32;  5. IoU with the "+1" pixel convention over (ground truth, kept detection) pairs of equal class:
+ *      ground-truth area in fp32, detection area in int32, intersection extents max(0, min - max + 1) and the quotient
+ *      inter / (ga + da - inter) in fp64, no contraction;  6. greedy matching: while the matrix maximum is > `iou` (strict,
+ *      fp64) its FIRST position in row-major order (rows: ground truths by index; columns: kept detections by descending
+ *      score) is matched and its row and column leave;  7. class k in [0, K): TP = matched ground truths, FP = kept
+ *      detections not matched, FN = ground truths not matched; other classes are counted nowhere.
+ * det_boxes [B,D,4] fp32 (x1,y1,x2,y2 at the model's output size), det_scores [B,D], det_classes [B,D] i32, det_count [B];
+ * gt_boxes [B,G,4], gt_classes [B,G], gt_count [B] (at the loader's size); counts above D / G are clamped, entries beyond
+ * the counts are never read.  scale [B,2] fp32 (sx, sy), clip_size [B,2] i32 (h, w).  D, G <= 100, 1 <= top_n <= D,
+ * 1 <= K <= 32, iou finite and >= 0.  counts [B,K,3] i32 (TP, FP, FN): every element is written. */
+int sfod_f1_count(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                  const int32_t* det_count, const float* gt_boxes, const int32_t* gt_classes,
+                  const int32_t* gt_count, const float* scale, const int32_t* clip_size, int B, int D, int G, int K,
+                  double iou, int top_n, float score, int32_t* counts, void* stream);
+
 /* Class-wise adaptive pseudo-label threshold: AdaptiveConfidenceBasedSelfTrainingLoss
  * (daod/modeling/adaptive_thresh/adaptive_confidence.py:6-34, "convex" curve) with the trainer's bookkeeping
  * (daod/engine/trainers/source_free_adaptive_teacher.py:282-295 count_label_prediction, :297-309

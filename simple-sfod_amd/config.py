@@ -400,6 +400,10 @@ def add_native_config(cfg):
                           generic weight-gradient kernels are summed through slabs in a fixed order, so a step is
                           bit-identical from run to run (the reference on CUDA is not: cuDNN / atomicAdd); costs one
                           more pass over the split partials of the 1x1 / linear gradients (fc1: 2 x 103 MB).
+    SFOD.EVALUATORS       what ``Trainer.build_evaluator`` builds, in order.  ("coco",) (default): the ``NewCOCOEvaluator``
+                          alone -> ``{"bbox": {...}}``.  ("coco", "f1") is the reference's list (base.py:133-151): a
+                          ``DatasetEvaluators`` of it and the ``F1Evaluator`` -> ``"bbox"`` and ``"F1 Score"``.  An
+                          unknown name, a repeated name or an empty tuple is a ValueError.
     """
     _C = cfg
     _C.SFOD = CN()
@@ -433,6 +437,8 @@ def add_native_config(cfg):
     _C.SFOD.FUSE_BN_INPUT = True
     # d2's EvalHook inside Trainer.train(): Trainer.test every TEST.EVAL_PERIOD iterations and after the last one
     _C.SFOD.EVAL_HOOK = True
+    # the evaluators of Trainer.test, by name: "coco" (NewCOCOEvaluator), "f1" (F1Evaluator, counted on the device)
+    _C.SFOD.EVALUATORS = ("coco",)
     # json file {"<dataset name>": {"json_file": ..., "image_root": ...}}: COCO-format datasets for the names in
     # DATASETS.*; names that are not registered fall back to the synthetic set (data/coco.py)
     _C.SFOD.DATASETS_FILE = ""

@@ -1671,6 +1671,151 @@ extern "C" int sfod_bpc_loss(const float* pred, int ld, int R, int K, const floa
                            loss, ws, 10.f, 10.f, 5.f, 5.f, 0, stream);
 }
 
+// F1Evaluator counts (daod/evaluation/f1_evaluator.py:38-173; include/sfod_hip.h has the rule), one wavefront per image:
+//   A  detector_postprocess to the loader's scale (fp32 multiply, clip, width and height > 0) and score >= thr (fp32);
+//   B  the top_n highest scores over all classes by rank counting (equal scores: the later index first); a kept detection's
+//      column IS its rank (the reference's columns are in descending score order), its box truncated to integers;
+//   C  the G x top_n matrix of "+1" IoUs in fp64 (fp32 ground-truth area, integer detection area; 0 where the classes
+//      differ) in LDS: 100 x 100 x 8 B = 80 000 B of the CU's 160 KiB;
+//   D  greedy rounds: the maximum and its first row-major position by a wavefront reduction on (value, -index); while it
+//      is > iou its row and column are marked and zeroed (iou >= 0, so a zero never matches again);
+//   E  lane k < K counts TP / FP / FN of class k and stores them (plain stores, no atomics).
+// Nothing is read beyond min(count, capacity); classes outside [0, K) take part in the matching among themselves (they
+// cannot touch another class's rows or columns) and are counted nowhere.
+#define F1_CAP 100      // == GT_CAP == TEST.DETECTIONS_PER_IMAGE
+
+__global__ void __launch_bounds__(64)
+k_f1_count(const float* __restrict__ dboxes, const float* __restrict__ dscores, const int32_t* __restrict__ dcls,
+           const int32_t* __restrict__ dcount, const float* __restrict__ gboxes, const int32_t* __restrict__ gcls,
+           const int32_t* __restrict__ gcount, const float* __restrict__ scale, const int32_t* __restrict__ clip,
+           int D, int G, int K, double iou_thr, int top_n, float score_thr, int32_t* __restrict__ counts) {
+  __shared__ double s_iou[F1_CAP * F1_CAP];
+  __shared__ float s_score[F1_CAP], s_gbox[F1_CAP][4], s_garea[F1_CAP];
+  __shared__ int s_ok[F1_CAP], s_tbox[F1_CAP][4], s_dbox[F1_CAP][4], s_dk[F1_CAP], s_dm[F1_CAP], s_gk[F1_CAP], s_gm[F1_CAP];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int nd = min(max(dcount[b], 0), D), ng = min(max(gcount[b], 0), G);
+  const float sx = scale[b * 2], sy = scale[b * 2 + 1];
+  const float h = (float)clip[b * 2], w = (float)clip[b * 2 + 1];
+  // A
+  int nvalid = 0;
+  for (int i0 = 0; i0 < nd; i0 += 64) {
+    const int i = i0 + lane;
+    bool ok = false;
+    if (i < nd) {
+      const Box o = load_box(dboxes + ((int64_t)b * D + i) * 4);
+      float x1 = o.x1 * sx, y1 = o.y1 * sy, x2 = o.x2 * sx, y2 = o.y2 * sy;
+      x1 = x1 < 0.f ? 0.f : (x1 > w ? w : x1);       // torch.clamp: NaN stays NaN and fails the size test below
+      y1 = y1 < 0.f ? 0.f : (y1 > h ? h : y1);
+      x2 = x2 < 0.f ? 0.f : (x2 > w ? w : x2);
+      y2 = y2 < 0.f ? 0.f : (y2 > h ? h : y2);
+      const float sc = dscores[(int64_t)b * D + i];
+      ok = (x2 - x1 > 0.f) && (y2 - y1 > 0.f) && (sc >= score_thr);
+      s_score[i] = sc;
+      s_ok[i] = ok;
+      if (ok) {                                      // inside [0, w] x [0, h]: the conversion truncates, never saturates
+        s_tbox[i][0] = (int)x1;
+        s_tbox[i][1] = (int)y1;
+        s_tbox[i][2] = (int)x2;
+        s_tbox[i][3] = (int)y2;
+      }
+    }
+    nvalid += __popcll(__ballot(ok));
+  }
+  const int nk = min(nvalid, top_n);
+  for (int g = lane; g < ng; g += 64) {
+    const Box e = load_box(gboxes + ((int64_t)b * G + g) * 4);
+    s_gbox[g][0] = e.x1;
+    s_gbox[g][1] = e.y1;
+    s_gbox[g][2] = e.x2;
+    s_gbox[g][3] = e.y2;
+    s_garea[g] = (e.x2 - e.x1 + 1.f) * (e.y2 - e.y1 + 1.f);
+    s_gk[g] = gcls[(int64_t)b * G + g];
+    s_gm[g] = 0;
+  }
+  for (int r = lane; r < nk; r += 64) s_dm[r] = 0;
+  __syncthreads();
+  // B
+  for (int i = lane; i < nd; i += 64) {
+    if (!s_ok[i]) continue;
+    const float sc = s_score[i];
+    int rank = 0;
+    for (int j = 0; j < nd; ++j) rank += (s_ok[j] && (s_score[j] > sc || (s_score[j] == sc && j > i))) ? 1 : 0;
+    if (rank < top_n) {
+      for (int c = 0; c < 4; ++c) s_dbox[rank][c] = s_tbox[i][c];
+      s_dk[rank] = dcls[(int64_t)b * D + i];
+    }
+  }
+  __syncthreads();
+  // C
+  const int n = ng * nk;
+  for (int idx = lane; idx < n; idx += 64) {
+    const int g = idx / nk, r = idx - g * nk;
+    double v = 0.0;
+    if (s_gk[g] == s_dk[r]) {
+      const int dx1 = s_dbox[r][0], dy1 = s_dbox[r][1], dx2 = s_dbox[r][2], dy2 = s_dbox[r][3];
+      const int32_t da = (int32_t)((int64_t)(dx2 - dx1 + 1) * (int64_t)(dy2 - dy1 + 1));
+      const double xx1 = fmax((double)s_gbox[g][0], (double)dx1), yy1 = fmax((double)s_gbox[g][1], (double)dy1);
+      const double xx2 = fmin((double)s_gbox[g][2], (double)dx2), yy2 = fmin((double)s_gbox[g][3], (double)dy2);
+      const double iw = fmax(0.0, xx2 - xx1 + 1.0), ih = fmax(0.0, yy2 - yy1 + 1.0);
+      const double inter = iw * ih;
+      v = inter / (((double)s_garea[g] + (double)da) - inter);
+    }
+    s_iou[idx] = v;
+  }
+  __syncthreads();
+  // D: at most min(ng, nk) rounds, each removes one row and one column
+  for (int round = 0; round < min(ng, nk); ++round) {
+    double best = -1.0;
+    int at = 0x7fffffff;
+    for (int idx = lane; idx < n; idx += 64) {
+      const double v = s_iou[idx];
+      if (v > best) { best = v; at = idx; }          // ascending idx per lane: the first maximum stays
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const double ov = __shfl_xor(best, off);
+      const int oa = __shfl_xor(at, off);
+      if (ov > best || (ov == best && oa < at)) { best = ov; at = oa; }
+    }
+    if (!(best > iou_thr)) break;                    // the same (best, at) in every lane
+    const int g = at / nk, r = at - g * nk;
+    for (int c = lane; c < nk; c += 64) s_iou[g * nk + c] = 0.0;
+    for (int q = lane; q < ng; q += 64) s_iou[q * nk + r] = 0.0;
+    if (lane == 0) { s_gm[g] = 1; s_dm[r] = 1; }
+    __syncthreads();
+  }
+  __syncthreads();
+  // E
+  if (lane < K) {
+    int tp = 0, fp = 0, fn = 0;
+    for (int g = 0; g < ng; ++g)
+      if (s_gk[g] == lane) { if (s_gm[g]) ++tp; else ++fn; }
+    for (int r = 0; r < nk; ++r)
+      if (s_dk[r] == lane && !s_dm[r]) ++fp;
+    int32_t* o = counts + ((int64_t)b * K + lane) * 3;
+    o[0] = tp;
+    o[1] = fp;
+    o[2] = fn;
+  }
+}
+
+extern "C" int sfod_f1_count(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                             const int32_t* det_count, const float* gt_boxes, const int32_t* gt_classes,
+                             const int32_t* gt_count, const float* scale, const int32_t* clip_size, int B, int D, int G,
+                             int K, double iou, int top_n, float score, int32_t* counts, void* stream) {
+  SFOD_REQUIRE_EXTENTS("f1_count", B, D, G, K, top_n);
+  SFOD_REQUIRE(D <= F1_CAP && G <= F1_CAP, "f1_count: at most 100 detections and 100 ground truths per image");
+  SFOD_REQUIRE(K >= 1 && K <= KMAX, "f1_count K");
+  SFOD_REQUIRE(top_n >= 1 && top_n <= D, "f1_count: top_n must lie in [1, D]");
+  SFOD_REQUIRE(iou >= 0.0 && iou <= 1.7e308, "f1_count: iou must be finite and >= 0");
+  SFOD_REQUIRE(score == score, "f1_count: score is NaN");
+  SFOD_REQUIRE(det_boxes && det_scores && det_classes && det_count && gt_boxes && gt_classes && gt_count && scale &&
+               clip_size && counts, "f1_count: null operand");
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(k_f1_count, dim3(B), dim3(64), 0, (hipStream_t)stream, det_boxes, det_scores, det_classes, det_count,
+                     gt_boxes, gt_classes, gt_count, scale, clip_size, D, G, K, iou, top_n, score, counts);
+  return sfod_check_launch("f1_count");
+}
+
 // Class-wise adaptive pseudo-label threshold (adaptive_thresh/adaptive_confidence.py:6-34 and the trainer's
 // bookkeeping, source_free_adaptive_teacher.py:282-309,393-404,461-466), one launch per step, no host sync:
 //   1. per-class count of this step's detections with score > thr -> ring row `row` of reserve [R][K]

@@ -451,14 +451,27 @@ class BaseTrainer:
     @classmethod
     def build_evaluator(cls, cfg, dataset_name, output_folder=None, data_loader=None):
         """``NewCOCOEvaluator`` for the "coco" evaluator type (base.py:133-142); the synthetic target set
-        stands in for the registered datasets (no dataset files in the build environment)."""
+        stands in for the registered datasets (no dataset files in the build environment).  ``SFOD.EVALUATORS`` names
+        what is built: the default ("coco",) returns that evaluator itself, more than one name a ``DatasetEvaluators``
+        (("coco", "f1") is the reference's list, base.py:149)."""
         from ..data import CITYSCAPES_CLASSES, TestLoader
-        from ..evaluation import NewCOCOEvaluator
-        loader = data_loader or TestLoader(cfg, torch.device("cpu"), dataset_name=dataset_name)
-        names = getattr(loader.dataset, "class_names", None) or CITYSCAPES_CLASSES[: cfg.MODEL.ROI_HEADS.NUM_CLASSES]
-        if len(names) < cfg.MODEL.ROI_HEADS.NUM_CLASSES:
-            names = [str(i) for i in range(cfg.MODEL.ROI_HEADS.NUM_CLASSES)]
-        return NewCOCOEvaluator(dataset_name, loader.dataset.dataset_dicts(cfg), names, output_dir=output_folder)
+        from ..evaluation import DatasetEvaluators, F1Evaluator, NewCOCOEvaluator
+        kinds = tuple(cfg.SFOD.EVALUATORS)
+        if not kinds:
+            raise ValueError("SFOD.EVALUATORS is empty: name at least one of 'coco', 'f1'")
+        for kind in kinds:
+            if kind not in ("coco", "f1") or kinds.count(kind) > 1:
+                raise ValueError(f"SFOD.EVALUATORS: unknown or repeated evaluator {kind!r} in {kinds} (built: 'coco', 'f1')")
+
+        def coco():
+            loader = data_loader or TestLoader(cfg, torch.device("cpu"), dataset_name=dataset_name)
+            names = getattr(loader.dataset, "class_names", None) or CITYSCAPES_CLASSES[: cfg.MODEL.ROI_HEADS.NUM_CLASSES]
+            if len(names) < cfg.MODEL.ROI_HEADS.NUM_CLASSES:
+                names = [str(i) for i in range(cfg.MODEL.ROI_HEADS.NUM_CLASSES)]
+            return NewCOCOEvaluator(dataset_name, loader.dataset.dataset_dicts(cfg), names, output_dir=output_folder)
+
+        built = [coco() if kind == "coco" else F1Evaluator(cfg.MODEL.ROI_HEADS.NUM_CLASSES) for kind in kinds]
+        return built[0] if len(built) == 1 else DatasetEvaluators(built)
 
     @classmethod
     def test(cls, cfg, model, evaluators=None):

@@ -8,7 +8,9 @@ IoU type, default parameters: IoU .50:.05:.95, 101 recall points, maxDets 1/10/1
 medium / large >96^2, crowd ground truth matched as "ignore" with intersection-over-detection-area).
 Parity unpinned: checked against hand-computed cases (``tests/test_evaluation.py``), not against pycocotools.
 Host-side numpy like the reference's (the model's forward is the device work); not on the timed path.
-The reference also appends an ``F1Evaluator`` (``base.py:149``); that one is not built.
+The reference also appends an ``F1Evaluator`` (``base.py:149``): built here as ``F1Evaluator`` (below), the one evaluator
+that counts on the device (``sfod_f1_count``) and reads back once, in ``evaluate()``; ``SFOD.EVALUATORS ("coco", "f1")``
+puts both behind ``DatasetEvaluators`` as the reference does.
 """
 import copy
 import itertools
@@ -17,6 +19,8 @@ from collections import OrderedDict, defaultdict
 
 import numpy as np
 import torch
+
+from .modeling.batched import GT_CAP, BatchedGT
 
 logger = logging.getLogger("sfod")
 
@@ -271,6 +275,193 @@ class NewCOCOEvaluator:
             per_category.append((name, float(ap * 100)))
             per_category.append((name + "_AP50", float(ap50 * 100)))
         results.update({"AP-" + name: ap for name, ap in per_category})
+        return results
+
+
+def f1_image_counts(det_boxes, det_scores, det_classes, gt_boxes, gt_classes, sx, sy, height, width, class_number,
+                    iou=0.5, top_n=5, score=0.5):
+    """The F1Evaluator's rule for ONE image in numpy (the host definition; ``sfod_f1_count`` is the same rule on the
+    device) -> [class_number, 3] int64 (TP, FP, FN).
+      1. ``detector_postprocess`` to the loader's scale: fp32 multiply by ``float32(sx)`` / ``float32(sy)``, clip to
+         [0, width] x [0, height], drop width <= 0 or height <= 0;  2. keep ``score_i >= float32(score)``;
+      3. the ``top_n`` highest scores over all classes (equal scores: the later index first; the reference's order among
+         them is whatever its unstable sort leaves);  4. detection coordinates truncated toward zero to int32;
+      5. "+1" IoU of (ground truth, kept detection) pairs of equal class: ground-truth area in fp32, detection area in
+         int32, intersection and quotient in fp64;  6. while the matrix maximum is > ``iou``: its first position in
+         row-major order (ground truths by index x detections by descending score) is a match, its row and column are
+         zeroed;  7. per class TP = matched ground truths, FP = kept detections not matched, FN = ground truths not matched;
+         classes outside [0, class_number) are counted nowhere."""
+    K = int(class_number)
+    f32 = np.float32
+    b = np.asarray(det_boxes, dtype=f32).reshape(-1, 4) * np.array([sx, sy, sx, sy], dtype=f32)
+    s = np.asarray(det_scores, dtype=f32).reshape(-1)
+    dk = np.asarray(det_classes).reshape(-1).astype(np.int64)
+    b[:, 0::2] = np.clip(b[:, 0::2], f32(0), f32(width))
+    b[:, 1::2] = np.clip(b[:, 1::2], f32(0), f32(height))
+    ok = np.nonzero((b[:, 2] - b[:, 0] > 0) & (b[:, 3] - b[:, 1] > 0) & (s >= f32(score)))[0]
+    keep = ok[np.lexsort((-ok, -s[ok]))][: int(top_n)]             # descending score, then descending index
+    d = b[keep].astype(np.int32)
+    dk = dk[keep]
+    g = np.asarray(gt_boxes, dtype=f32).reshape(-1, 4)
+    gk = np.asarray(gt_classes).reshape(-1).astype(np.int64)
+    gm, dm = np.zeros(len(g), dtype=bool), np.zeros(len(d), dtype=bool)
+    if len(g) and len(d):
+        ga = (g[:, 2] - g[:, 0] + f32(1)) * (g[:, 3] - g[:, 1] + f32(1))                      # fp32
+        da = (d[:, 2] - d[:, 0] + 1) * (d[:, 3] - d[:, 1] + 1)                                # int32
+        g64, d64 = g.astype(np.float64), d.astype(np.float64)
+        iw = np.maximum(0.0, np.minimum(g64[:, None, 2], d64[None, :, 2]) - np.maximum(g64[:, None, 0], d64[None, :, 0]) + 1)
+        ih = np.maximum(0.0, np.minimum(g64[:, None, 3], d64[None, :, 3]) - np.maximum(g64[:, None, 1], d64[None, :, 1]) + 1)
+        inter = iw * ih
+        m = inter / ((ga.astype(np.float64)[:, None] + da.astype(np.float64)[None, :]) - inter)
+        m[gk[:, None] != dk[None, :]] = 0.0
+        while True:
+            at = int(np.argmax(m))                                 # the first maximum in row-major order
+            i, j = divmod(at, len(d))
+            if not m[i, j] > float(iou):
+                break
+            m[i, :] = 0.0
+            m[:, j] = 0.0
+            gm[i] = dm[j] = True
+    out = np.zeros((K, 3), dtype=np.int64)
+    gin, din = (gk >= 0) & (gk < K), (dk >= 0) & (dk < K)
+    out[:, 0] = np.bincount(gk[gin & gm], minlength=K)
+    out[:, 1] = np.bincount(dk[din & ~dm], minlength=K)
+    out[:, 2] = np.bincount(gk[gin & ~gm], minlength=K)
+    return out
+
+
+class F1Evaluator:
+    """``F1Evaluator(class_number, iou=0.5, top_n=5, score=0.5)`` (``daod/evaluation/f1_evaluator.py``): d2's ``reset`` /
+    ``process`` / ``evaluate`` protocol; ``evaluate`` returns ``{"F1 Score": 2pr / (p + r)}`` from the TP / FP / FN summed
+    over images and classes (``f1_image_counts`` has the rule).  Device tensors are packed into the fixed-capacity layout
+    with torch ops and counted by ``native.f1_count`` into a device accumulator: no host synchronisation before
+    ``evaluate()``, which makes the one device-to-host copy.  Host tensors (``MODEL.DEVICE cpu``) run the numpy rule.
+    ``counts`` ([class_number, 3] int64: TP, FP, FN per class) holds the table behind the last ``evaluate()``.
+    Ranks: the reference scores rank 0's share only (nothing is gathered); here the counts are summed over the ranks
+    with one all-reduce, the dict is returned on rank 0 and ``{}`` elsewhere."""
+
+    def __init__(self, class_number, iou=0.5, top_n=5, score=0.5, distributed=True):
+        self.class_number, self.iou, self.top_n, self.score = int(class_number), iou, top_n, score
+        self._distributed = distributed
+        self.reset()
+
+    def reset(self):
+        self._host = np.zeros((self.class_number, 3), dtype=np.int64)
+        self._dev = None
+        self.counts = np.zeros((self.class_number, 3), dtype=np.int64)
+
+    def process(self, inputs, outputs):
+        pairs = [(i["instances"], o["instances"]) for i, o in zip(inputs, outputs) if "instances" in o]
+        if not pairs:
+            return
+        pairs = [(gi.materialize() if hasattr(gi, "materialize") else gi, oi) for gi, oi in pairs]
+        B, cap = len(pairs), GT_CAP
+        for gi, oi in pairs:
+            if len(oi) > cap or len(gi) > cap:
+                raise ValueError(f"F1Evaluator: more than {cap} detections or ground-truth boxes in one image "
+                                 f"({len(oi)}, {len(gi)})")
+        dev = pairs[0][1].scores.device
+        pin = dev.type == "cuda"
+        nds, ngs = [len(oi) for _, oi in pairs], [len(gi) for gi, _ in pairs]
+        N, M = sum(nds), sum(ngs)
+        # lengths, sizes, scales and the rows each image's entries go to are host numbers (tensor shapes,
+        # Instances.image_size): staged in pinned memory and uploaded without blocking.  The detection and ground-truth
+        # values never leave the device: one concatenation and one row scatter per field for the whole batch
+        ints = torch.empty(4 * B, dtype=torch.int32, pin_memory=pin)          # det counts | gt counts | clip (h, w) x B
+        rows = torch.empty(N + M, dtype=torch.int64, pin_memory=pin)          # flat [B * cap] rows: detections | ground truth
+        scale = torch.empty(B, 2, dtype=torch.float32, pin_memory=pin)
+        ints_h, rows_h, scale_h = ints.numpy(), rows.numpy(), scale.numpy()
+        ints_h[:B], ints_h[B:2 * B] = nds, ngs
+        ints_h[2 * B:] = [int(v) for gi, _ in pairs for v in gi.image_size]
+        rows_h[:N] = np.concatenate([i * cap + np.arange(n) for i, n in enumerate(nds)])
+        rows_h[N:] = np.concatenate([i * cap + np.arange(n) for i, n in enumerate(ngs)])
+        scale_h[:] = [(gi.image_size[1] / oi.image_size[1], gi.image_size[0] / oi.image_size[0])
+                      for gi, oi in pairs]                                    # detector_postprocess(out, *input size)
+        ints, rows, scale = (t.to(dev, non_blocking=True) for t in (ints, rows, scale))
+
+        def scatter(parts, idx, dtype, *tail):
+            out = torch.empty(B * cap, *tail, dtype=dtype, device=dev)
+            if len(idx):
+                out.index_copy_(0, idx, torch.cat([p.detach() for p in parts]).to(device=dev, dtype=dtype, non_blocking=True))
+            return out.view(B, cap, *tail)
+        db = scatter([oi.pred_boxes.tensor for _, oi in pairs], rows[:N], torch.float32, 4)
+        ds = scatter([oi.scores for _, oi in pairs], rows[:N], torch.float32)
+        dc = scatter([oi.pred_classes for _, oi in pairs], rows[:N], torch.int32)
+        gb = scatter([gi.gt_boxes.tensor for gi, _ in pairs], rows[N:], torch.float32, 4)
+        gc = scatter([gi.gt_classes for gi, _ in pairs], rows[N:], torch.int32)
+        gt = BatchedGT(gb, gc, ints[B:2 * B], [tuple(gi.image_size) for gi, _ in pairs])
+        self.process_batched(db, ds, dc, ints[:B], gt, scale, ints[2 * B:].view(B, 2))
+
+    def process_batched(self, det_boxes, det_scores, det_classes, det_count, gt, scale, clip_size):
+        """Container-level entry: detections as fixed-capacity arrays ([B,D,4] fp32, [B,D] fp32, [B,D] int32, [B] int32),
+        ground truth as a ``BatchedGT``, ``scale`` [B,2] fp32 (sx, sy) and ``clip_size`` [B,2] int32 (h, w)."""
+        if det_boxes.is_cuda:
+            from . import native
+            c = native.f1_count(det_boxes, det_scores, det_classes, det_count, gt.boxes, gt.classes, gt.count, scale,
+                                clip_size, self.class_number, self.iou, self.top_n, self.score)
+            c = c.sum(dim=0, dtype=torch.int64)
+            self._dev = c if self._dev is None else self._dev + c
+            return
+        db, ds, dc = det_boxes.numpy(), det_scores.numpy(), det_classes.numpy()
+        gb, gc = gt.boxes.numpy(), gt.classes.numpy()
+        sc, cl = np.asarray(scale, dtype=np.float32), np.asarray(clip_size)
+        nd = np.clip(np.asarray(det_count), 0, db.shape[1])
+        ng = np.clip(np.asarray(gt.count), 0, gb.shape[1])
+        for i in range(db.shape[0]):
+            self._host += f1_image_counts(db[i, :nd[i]], ds[i, :nd[i]], dc[i, :nd[i]], gb[i, :ng[i]], gc[i, :ng[i]],
+                                          sc[i, 0], sc[i, 1], int(cl[i, 0]), int(cl[i, 1]), self.class_number, self.iou,
+                                          self.top_n, self.score)
+
+    def accumulated(self):
+        """This rank's [class_number, 3] int64 table so far (copies the device accumulator to the host)."""
+        return self._host.copy() if self._dev is None else self._host + self._dev.cpu().numpy()
+
+    def evaluate(self):
+        dist = torch.distributed
+        if self._distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            on_dev = self._dev is not None and "nccl" in str(dist.get_backend())
+            t = torch.from_numpy(self._host.copy())
+            t = self._dev + t.to(self._dev.device) if on_dev else (t if self._dev is None else t + self._dev.cpu())
+            dist.all_reduce(t)
+            self.counts = t.cpu().numpy()
+            if dist.get_rank() != 0:
+                return {}
+        else:
+            self.counts = self.accumulated()
+        tp, fp, fn = (int(v) for v in self.counts.sum(axis=0))
+        precision = 0 if tp + fp == 0 else tp / (tp + fp)
+        recall = 0 if tp + fn == 0 else tp / (tp + fn)
+        if precision + recall == 0:
+            return {"F1 Score": 0}
+        return {"F1 Score": 2 * (precision * recall) / (precision + recall)}
+
+
+class DatasetEvaluators:
+    """d2 ``DatasetEvaluators``: ``reset`` / ``process`` go to every evaluator; ``evaluate`` merges their dicts on the main
+    process (a key two evaluators both return is an error) and is an empty ``OrderedDict`` elsewhere."""
+
+    def __init__(self, evaluators):
+        self._evaluators = list(evaluators)
+
+    def reset(self):
+        for e in self._evaluators:
+            e.reset()
+
+    def process(self, inputs, outputs):
+        for e in self._evaluators:
+            e.process(inputs, outputs)
+
+    def evaluate(self):
+        dist = torch.distributed
+        main = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+        results = OrderedDict()
+        for e in self._evaluators:
+            result = e.evaluate()
+            if main and result is not None:
+                for k, v in result.items():
+                    if k in results:
+                        raise ValueError("Different evaluators produce results with the same key {}".format(k))
+                    results[k] = v
         return results
 
 

@@ -93,6 +93,8 @@ def parse_header(path=HEADER):
                     argtypes.append(ctypes.c_int64)
                 elif a.startswith("float"):
                     argtypes.append(ctypes.c_float)
+                elif a.startswith("double"):
+                    argtypes.append(ctypes.c_double)
                 elif a.startswith("int") or a.startswith("int32_t"):
                     argtypes.append(ctypes.c_int)
                 else:
@@ -1428,6 +1430,24 @@ def bpc_loss(pred, K, rois, roi_cls, sizes_dev, gt_boxes, gt_classes, gt_count, 
         call("sfod_bpc_loss_opt", pred, pred.shape[-1], pred.shape[0], K, rois, roi_cls, B, sizes_dev, gt_boxes,
              gt_classes, gt_count, G, float(iou_thresh), loss, ws, *box_reg.weights, int(box_reg.cls_agnostic))
     return loss[0]
+
+
+def f1_count(det_boxes, det_scores, det_classes, det_count, gt_boxes, gt_classes, gt_count, scale, clip_size, K,
+             iou=0.5, top_n=5, score=0.5):
+    """F1Evaluator's per-image, per-class (TP, FP, FN) of a batch of fixed-capacity arrays -> [B, K, 3] int32 (no host
+    synchronisation; include/sfod_hip.h: sfod_f1_count)."""
+    B, D = det_scores.shape
+    G = gt_classes.shape[1]
+    assert det_boxes.dtype == torch.float32 and det_scores.dtype == torch.float32 and gt_boxes.dtype == torch.float32
+    assert det_classes.dtype == torch.int32 and det_count.dtype == torch.int32
+    assert gt_classes.dtype == torch.int32 and gt_count.dtype == torch.int32
+    assert scale.dtype == torch.float32 and clip_size.dtype == torch.int32
+    assert det_boxes.shape == (B, D, 4) and det_classes.shape == (B, D) and gt_boxes.shape == (B, G, 4)
+    assert det_count.shape == (B,) and gt_count.shape == (B,) and scale.shape == (B, 2) and clip_size.shape == (B, 2)
+    counts = torch.empty(B, K, 3, dtype=torch.int32, device=det_boxes.device)
+    call("sfod_f1_count", det_boxes, det_scores, det_classes, det_count, gt_boxes, gt_classes, gt_count, scale, clip_size,
+         B, D, G, K, float(iou), int(top_n), float(score), counts)
+    return counts
 
 
 def predict_probs(scores):

@@ -19,13 +19,14 @@ def main():
     ap.add_argument("--images", type=int, default=64)
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--evaluators", default="coco", help="SFOD.EVALUATORS, comma separated: coco | coco,f1")
     args = ap.parse_args()
     sfod = importlib.import_module("simple-sfod_amd")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cfg = sfod.config.setup_cfg(
         os.path.join(root, "configs", "faster_rcnn_VGG_cityscapes_foggy_adaptive_teacher_source_free.yaml"),
         ["OUTPUT_DIR", "", "SFOD.COMPUTE_DTYPE", args.dtype, "TEST.IMS_PER_BATCH", str(args.batch), "SFOD.SYNTHETIC.NUM_TEST_IMAGES", str(args.images),
-         "DATASETS.TEST", "('synthetic_cityscapes_foggy_val',)"])
+         "DATASETS.TEST", "('synthetic_cityscapes_foggy_val',)", "SFOD.EVALUATORS", repr(tuple(args.evaluators.split(",")))])
     torch.manual_seed(0)
     T = sfod.engine.BaseTrainer
     model = T.build_model(cfg)
@@ -50,11 +51,16 @@ def main():
         t1 = time.perf_counter()
     res = evaluator.evaluate()
     t2 = time.perf_counter()
-    print(json.dumps({"metric": "eval-mode inference images/s (incl. postprocess + evaluator.process)",
-                      "value": round(n / (t1 - t0), 2), "unit": "images/s", "n_gpus": 1, "batch": args.batch,
-                      "images": n, "ap_table_seconds": round(t2 - t1, 3),
-                      "detections": len([d for p in evaluator._predictions for d in p["instances"]]),
-                      "AP50": res["bbox"]["AP50"], "dtype": cfg.SFOD.COMPUTE_DTYPE, "data": "synthetic"}))
+    coco = getattr(evaluator, "_evaluators", [evaluator])[0]
+    out = {"metric": "eval-mode inference images/s (incl. postprocess + evaluator.process)",
+           "value": round(n / (t1 - t0), 2), "unit": "images/s", "n_gpus": 1, "batch": args.batch,
+           "images": n, "ap_table_seconds": round(t2 - t1, 3),
+           "detections": len([d for p in coco._predictions for d in p["instances"]]),
+           "AP50": res["bbox"]["AP50"], "dtype": cfg.SFOD.COMPUTE_DTYPE, "data": "synthetic",
+           "evaluators": list(cfg.SFOD.EVALUATORS)}
+    if "F1 Score" in res:
+        out["F1 Score"] = res["F1 Score"]
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
