@@ -121,9 +121,11 @@ int sfod_conv_fwd_scratch(const void* x, const void* w, const uint32_t* w_absmax
 int sfod_conv_stats_blocks(int B, int H, int W, int Cin, int Cout, int ksize, int dt);
 /* kernel selection for 3x3 bf16 convolutions: 0 auto, 1 generic implicit GEMM (im2col chunks
  * DMA'd per tap), 2 halo-patch kernel (input patch staged once per 32-channel slice and reused by
- * all nine taps) whenever the shape allows, 3 / 4 auto without / with the wide-tile bf16x3
- * weight gradient wherever it applies.  For A/B tests
- * and benchmarks. */
+ * all nine taps) whenever the shape allows.  3 / 4: auto for everything but the generic bf16x3 weight
+ * gradient (1x1 / linear layers, 3x3 layers the halo-patch kernel does not take), which then ALWAYS runs
+ * its 64 x 64 kernel (3: k_conv_wgrad<bf16_t,2,2,1>) / its wide 128 x 256 kernel wherever the operands
+ * allow it, i.e. Cout >= 128 and ksize^2 * Cin >= 256 (4: k_conv_wgrad_x3w), instead of choosing by the
+ * size of the output.  Any other value means 0.  For A/B tests and benchmarks. */
 int sfod_set_conv_algo(int algo);
 /* Data gradient of a 3x3 convolution with the BatchNorm-backward REDUCTION of the layer below folded into its epilogue
  * (the hand-written backward of vgg.py's conv-BN-ReLU chain; torch autograd runs these as separate kernels).
@@ -212,7 +214,11 @@ int sfod_conv_first_fused_ws(const void* x, const void* w, const uint32_t* w_abs
 /* weight gradient: dw[n][tap][c] += sum_m dy[m][n] * x[pix(m)+tap][c]  (fp32, packed layout, added
  * into the caller's (zero-initialised) buffer).  3x3 bf16 layers run the halo-patch kernel: pixel
  * splits write fp32 slabs into `ws` (sfod_conv_wgrad_ws_bytes, may be 0 -> ws unused) and are summed
- * in a fixed order; other shapes use the generic kernel (split over row chunks, float atomics). */
+ * in a fixed order; other shapes use the generic kernel (split over row chunks, float atomics).
+ * A batch whose x or dy passes the kernel's 32-bit byte offsets is walked in sub-batches inside the one
+ * call; sfod_conv_wgrad_ws_bytes is the LARGEST need of any sub-batch (a smaller remainder can want more
+ * slabs than a full one), and a smaller workspace is refused before anything is launched.  0 for hostile
+ * extents and for an empty gradient (no pixels, no input or output channels, ksize 0). */
 int64_t sfod_conv_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int lddy, int dt);
 int sfod_conv_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int Cin,
                     int Cout, int ksize, int lddy, int dt, void* ws, int64_t ws_bytes, void* stream);

@@ -502,7 +502,8 @@ static int ilog2_exact(int v) {
 }
 
 // process-wide kernel-selection knob for A/B runs and tests (0 auto, 1 generic implicit GEMM only, 2 halo-patch kernel
-// whenever the shape allows); a relaxed atomic word -- every choice computes the same values
+// whenever the shape allows, 3 / 4 auto with the generic weight gradient forced to its 64 x 64 / its wide kernel:
+// ConvWgradPlan::force); a relaxed atomic word -- every choice computes the same values
 static std::atomic<int> g_conv_algo_v{0};
 #define g_conv_algo (g_conv_algo_v.load(std::memory_order_relaxed))
 extern "C" int sfod_set_conv_algo(int algo) { g_conv_algo_v.store(algo, std::memory_order_relaxed); return 0; }
@@ -1351,52 +1352,6 @@ k_conv_wgrad_x3w(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, fl
     }
 }
 
-static bool use_patch_wgrad(const W3Plan& p, int ksize, int dt) {
-  if (ksize != 3 || !is_bf16_storage(dt) || dt == SFOD_F16X3 || !p.ok || g_conv_algo == 1) return false;
-  if (g_conv_algo == 2) return true;
-  // tiny problems: not enough pixel tiles to give every (co, ci) block a few tiles per split
-  return p.nsplit * p.tiles_per_split >= 3;
-}
-
-// The halo-patch weight-gradient kernel addresses x / dy with 32-bit byte offsets, so a batch whose tensors exceed
-// 2 GiB (B = 8 frames of 1024x2048 at 64 / 128 channels) is processed in sub-batches of `nb` images: each sub-launch
-// writes its slabs and the slab reduction of every sub-batch but the first accumulates.  -> plan of the first (largest)
-// sub-batch; nb = images per sub-batch (0: the shape is not served by the kernel at all).
-static W3Plan w3_plan_chunked(int B, int H, int W, int Cin, int Cout, int ksize, int lddy, int dt, int& nb) {
-  nb = 0;
-  W3Plan p;
-  p.ok = 0;
-  if (ksize != 3 || !is_bf16_storage(dt) || dt == SFOD_F16X3 || (int64_t)B * H * W == 0) return p;   // half pairs: forward only
-  const int split = (dt == SFOD_BF16X3);
-  for (int n = B; n >= 1; n = (n == 1) ? 0 : (n + 1) / 2) {
-    p = sfod_w3_plan(n, H, W, Cin, Cout, lddy, split);
-    if (p.ok) { nb = n; break; }
-  }
-  if (!p.ok || !use_patch_wgrad(p, ksize, dt)) { nb = 0; p.ok = 0; }
-  return p;
-}
-
-static int w3_launch_chunked(const void* x, const void* dy, float* dw, void* ws, int64_t ws_bytes, int B, int H, int W,
-                             int Cin, int Cout, int lddy, int dt, int out_mode, int nb, hipStream_t s) {
-  const int split = (dt == SFOD_BF16X3);
-  const int64_t eb = split ? 4 : 2;
-  for (int b0 = 0; b0 < B; b0 += nb) {
-    const int n = (B - b0 < nb) ? (B - b0) : nb;
-    const W3Plan p = sfod_w3_plan(n, H, W, Cin, Cout, lddy, split);
-    if (!p.ok || ws == nullptr || ws_bytes < p.ws_bytes) {
-      sfod_set_error("wgrad: workspace too small (sfod_conv_wgrad_ws_bytes)");
-      return SFOD_EBADARG;
-    }
-    const char* xb = (const char*)x + (int64_t)b0 * H * W * Cin * eb;
-    const char* dyb = (const char*)dy + (int64_t)b0 * H * W * lddy * eb;
-    // out_mode 0 (packed, += ) always accumulates; 1 (OIHW overwrite) becomes 2 (OIHW +=) after the first sub-batch
-    const int mode = (b0 == 0) ? out_mode : (out_mode == 1 ? 2 : out_mode);
-    const int rc = sfod_w3_launch(p, xb, dyb, dw, ws, n, H, W, Cin, Cout, lddy, mode, s, split);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
 // ---- deterministic mode (SFOD.DETERMINISTIC / SFOD_DETERMINISTIC=1): no float atomics in any weight / bias gradient -----
 // The halo-patch 3x3 weight gradient always sums its pixel splits through slabs in a fixed order; the generic kernels (1x1,
 // linear, first layer, fp32) combine theirs with float atomics, whose arrival order differs from run to run.  In this mode
@@ -1427,16 +1382,19 @@ __global__ void __launch_bounds__(256) k_wgrad_slab_sum(const float* __restrict_
   }
 }
 
-// pixel splits + tile counts of the generic weight-gradient launch (the one rule for the launch and the workspace query)
+// which generic kernel: sfod_set_conv_algo(3) / (4) force the 64 x 64 / the 128 x 256 one wherever the operands allow it
+// (A/B runs: tools/experiments/r101_wgrad_1x1.py); every other setting leaves the choice to the size of the output
+enum WgradTile { WGRAD_TILE_AUTO, WGRAD_TILE_64, WGRAD_TILE_WIDE };
+// pixel splits + tile counts of the generic weight-gradient launch
 struct GenWgradPlan { int wide, tiles_n, tiles_m, splits, pps; };
-static GenWgradPlan gen_wgrad_plan(int M, int Cout, int Ntot, int dt) {
+static GenWgradPlan gen_wgrad_plan(int M, int Cout, int Ntot, int dt, WgradTile force) {
   GenWgradPlan g;
   const int split = (dt == SFOD_BF16X3);
   // wide tiles pay off when the OUTPUT is big (fc1: 1024 x 25088 -> 784 tiles; 1.29 -> 1.02 ms); a small output with a
   // long pixel axis (1x1 bottleneck convolutions, fc2) needs many pixel splits either way and the 64 x 64 kernel's
-  // shorter prologue wins there (profiles/r2d_bench_wgrad.txt).  algo 3: A/B hook, always the 64 x 64 kernel
-  g.wide = split && Cout >= 128 && Ntot >= 256 && g_conv_algo != 3 &&
-           (g_conv_algo == 4 || (int64_t)((Ntot + 255) / 256) * ((Cout + 127) / 128) >= 256);
+  // shorter prologue wins there (profiles/r2d_bench_wgrad.txt)
+  g.wide = split && Cout >= 128 && Ntot >= 256 && force != WGRAD_TILE_64 &&
+           (force == WGRAD_TILE_WIDE || (int64_t)((Ntot + 255) / 256) * ((Cout + 127) / 128) >= 256);
   if (g.wide) {
     // wide layers: 128 x 256 tiles, one 8-wave workgroup per CU.  Pixel splits: the fewest that fill >= 85 % of the
     // last round of 256 workgroups (more splits = more float-atomic traffic), each at least 8 stages long
@@ -1474,25 +1432,84 @@ static GenWgradPlan gen_wgrad_plan(int M, int Cout, int Ntot, int dt) {
   return g;
 }
 
-extern "C" int64_t sfod_conv_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int lddy, int dt) {
-  if (!(conv_shape_fits(B, H, W, Cin, Cout, ksize) && sfod_ints_ok({lddy}))) return 0;      // hostile extents: not served / nothing
-  int nb = 0;
-  if (dt != SFOD_F32) {
-    const W3Plan p = w3_plan_chunked(B, H, W, Cin, Cout, ksize, lddy, dt, nb);
-    if (nb > 0) return p.ws_bytes;      // the first sub-batch is the largest
+// ---- the one rule behind every weight-gradient query and launch ---------------------------------------------------------
+// Which kernel serves a weight gradient, in which sub-batches and splits, and how much workspace it wants: the three
+// queries read a plan, the three launches are driven by one, and none of them plans its shape a second time.
+enum WgradKind { WGRAD_NONE, WGRAD_PATCH, WGRAD_GEMM, WGRAD_GEMM_WIDE };   // NONE: hostile extents or an empty gradient
+struct ConvWgradPlan {
+  WgradKind kind = WGRAD_NONE;
+  // WGRAD_PATCH.  The halo-patch kernel addresses x / dy with 32-bit byte offsets, so a batch whose tensors exceed 2 GiB
+  // (B = 8 frames of 1024x2048 at 64 / 128 channels) is walked in sub-batches of `nb` images: each sub-launch writes its
+  // slabs, and the slab reduction of every sub-batch but the first accumulates.  full: the plan of a sub-batch of nb
+  // images; rest: of the last one when B % nb != 0 (ok = 0: there is none).  The split count is not monotone in the
+  // number of tiles, so the smaller remainder may want MORE slabs than a full sub-batch: ws_bytes covers both.
+  int nb = 0; W3Plan full{}, rest{};
+  bool first_bn_ok = false;                 // k_first_wgrad_bn reproduces the two-launch path of this shape (one sub-batch)
+  // WGRAD_GEMM / WGRAD_GEMM_WIDE (k_conv_wgrad / k_conv_wgrad_x3w)
+  WgradTile force = WGRAD_TILE_AUTO;        // sfod_set_conv_algo(3) / (4)
+  GenWgradPlan gen{};
+  int cpt_shift = 0;                        // ksize 3: log2(Cin / chunk); -1: not a power of two, the launch is refused
+  bool slabs = false;                       // deterministic mode: every split but a lone one stores into a slab of its own
+  int64_t ws_bytes = 0;                     // the largest need of any sub-launch
+};
+
+static ConvWgradPlan conv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int ksize, int lddy, int dt) {
+  ConvWgradPlan p;
+  if (!(conv_shape_fits(B, H, W, Cin, Cout, ksize) && sfod_ints_ok({lddy}))) return p;      // hostile extents: not served / nothing
+  const int M = (int)((int64_t)B * H * W), Ntot = ksize * ksize * Cin, algo = g_conv_algo;
+  if (M == 0 || Ntot == 0 || Cout == 0) return p;      // an empty gradient
+  if (ksize == 3 && is_bf16_storage(dt) && dt != SFOD_F16X3 && algo != 1) {      // half pairs: forward only
+    const int split = (dt == SFOD_BF16X3);
+    int nb = B;
+    W3Plan full = sfod_w3_plan(nb, H, W, Cin, Cout, lddy, split), rest{};
+    while (!full.ok && nb > 1) { nb = (nb + 1) / 2; full = sfod_w3_plan(nb, H, W, Cin, Cout, lddy, split); }
+    if (full.ok && B % nb != 0) rest = sfod_w3_plan(B % nb, H, W, Cin, Cout, lddy, split);
+    // tiny problems stay on the generic kernel: not enough pixel tiles to give every (co, ci) block a few tiles per split
+    if (full.ok && (B % nb == 0 || rest.ok) && (algo == 2 || full.nsplit * full.tiles_per_split >= 3)) {
+      p.kind = WGRAD_PATCH; p.nb = nb; p.full = full; p.rest = rest;
+      p.ws_bytes = std::max(full.ws_bytes, rest.ok ? rest.ws_bytes : 0);
+      // one sub-batch only: the batch's M is the BatchNorm's
+      p.first_bn_ok = split && nb == B && lddy == Cout && sfod_w3_bn_ok(full, Cin, Cout);
+      return p;
+    }
   }
+  p.force = (algo == 3) ? WGRAD_TILE_64 : (algo == 4 ? WGRAD_TILE_WIDE : WGRAD_TILE_AUTO);
+  p.gen = gen_wgrad_plan(M, Cout, Ntot, dt, p.force);
+  p.kind = p.gen.wide ? WGRAD_GEMM_WIDE : WGRAD_GEMM;
+  if (ksize == 3) p.cpt_shift = ilog2_exact(Cin / (dt == SFOD_F32 ? 4 : 8));
   // the generic kernel accumulates with float atomics straight into dw -- unless the deterministic mode wants slabs
-  if (!sfod_deterministic() || (int64_t)B * H * W == 0) return 0;
-  const int Ntot = ksize * ksize * Cin;
-  const GenWgradPlan g = gen_wgrad_plan(B * H * W, Cout, Ntot, dt);
-  return g.splits > 1 ? (int64_t)g.splits * Cout * Ntot * 4 : 0;
+  p.slabs = sfod_deterministic() && p.gen.splits > 1;
+  if (p.slabs) p.ws_bytes = (int64_t)p.gen.splits * Cout * Ntot * 4;
+  return p;
+}
+
+extern "C" int64_t sfod_conv_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int lddy, int dt) {
+  return conv_wgrad_plan(B, H, W, Cin, Cout, ksize, lddy, dt).ws_bytes;
 }
 
 extern "C" int sfod_conv_wgrad_oihw_supported(int B, int H, int W, int Cin, int Cout, int ksize, int lddy, int dt) {
-  if (!(conv_shape_fits(B, H, W, Cin, Cout, ksize) && sfod_ints_ok({lddy}))) return 0;      // hostile extents: not served / nothing
-  int nb;
-  w3_plan_chunked(B, H, W, Cin, Cout, ksize, lddy, dt, nb);
-  return nb > 0 ? 1 : 0;
+  return conv_wgrad_plan(B, H, W, Cin, Cout, ksize, lddy, dt).kind == WGRAD_PATCH ? 1 : 0;
+}
+
+// WGRAD_PATCH: one sfod_w3_launch per sub-batch (out_mode as there)
+static int wgrad_patch_launch(const ConvWgradPlan& p, const void* x, const void* dy, float* dw, void* ws, int64_t ws_bytes,
+                              int B, int H, int W, int Cin, int Cout, int lddy, int dt, int out_mode, hipStream_t s) {
+  if (ws == nullptr || ws_bytes < p.ws_bytes) {
+    sfod_set_error("wgrad: workspace too small (sfod_conv_wgrad_ws_bytes)");
+    return SFOD_EBADARG;
+  }
+  const int split = (dt == SFOD_BF16X3);
+  const int64_t eb = split ? 4 : 2;
+  for (int b0 = 0; b0 < B; b0 += p.nb) {
+    const int n = std::min(p.nb, B - b0);
+    const char* xb = (const char*)x + (int64_t)b0 * H * W * Cin * eb;
+    const char* dyb = (const char*)dy + (int64_t)b0 * H * W * lddy * eb;
+    // out_mode 0 (packed, += ) always accumulates; 1 (OIHW overwrite) becomes 2 (OIHW +=) after the first sub-batch
+    const int mode = (b0 == 0) ? out_mode : (out_mode == 1 ? 2 : out_mode);
+    const int rc = sfod_w3_launch(n == p.nb ? p.full : p.rest, xb, dyb, dw, ws, n, H, W, Cin, Cout, lddy, mode, s, split);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 extern "C" int sfod_conv_wgrad_oihw(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin,
@@ -1503,11 +1520,11 @@ extern "C" int sfod_conv_wgrad_oihw(const void* x, const void* dy, float* dw_oih
                "conv_wgrad_oihw: negative or oversized extent");
   SFOD_REQUIRE(x != nullptr && dy != nullptr && dw_oihw != nullptr, "conv_wgrad_oihw: null operand");
   SFOD_REQUIRE(lddy >= Cout, "conv_wgrad_oihw: lddy < Cout");
-  int nb;
-  w3_plan_chunked(B, H, W, Cin, Cout, ksize, lddy, dt, nb);
-  SFOD_REQUIRE(nb > 0, "wgrad_oihw: shape not served by the halo-patch kernel (query sfod_conv_wgrad_oihw_supported)");
-  return w3_launch_chunked(x, dy, dw_oihw, ws, ws_bytes, B, H, W, Cin, Cout, lddy, dt, accumulate ? 2 : 1, nb,
-                           (hipStream_t)stream);
+  const ConvWgradPlan p = conv_wgrad_plan(B, H, W, Cin, Cout, ksize, lddy, dt);
+  SFOD_REQUIRE(p.kind == WGRAD_PATCH,
+               "wgrad_oihw: shape not served by the halo-patch kernel (query sfod_conv_wgrad_oihw_supported)");
+  return wgrad_patch_launch(p, x, dy, dw_oihw, ws, ws_bytes, B, H, W, Cin, Cout, lddy, dt, accumulate ? 2 : 1,
+                            (hipStream_t)stream);
 }
 
 // ---- first layer: weight gradient straight from the BatchNorm backward's inputs (k_first_wgrad_bn) ------------------
@@ -1516,21 +1533,9 @@ extern "C" int sfod_conv_wgrad_oihw(const void* x, const void* dy, float* dw_oih
 static SfodKnob g_first_wgrad_fused{"SFOD_FIRST_WGRAD_FUSED", 1, sfod_knob_bool};
 extern "C" int sfod_set_first_wgrad_fused(int on) { g_first_wgrad_fused.set(on); return 0; }
 
-// the plan of the two-launch path when the fused kernel reproduces it, else ok = 0
-static W3Plan first_wgrad_bn_plan(int B, int H, int W, int Cin, int Cout, int pool, int dt, int y_dt) {
-  W3Plan p;
-  p.ok = 0;
-  if (!(conv_shape_fits(B, H, W, Cin, Cout, 3) && sfod_ints_ok({pool, dt, y_dt}))) return p;
-  if (Cin != 8 || Cout != 64 || pool != 0 || dt != SFOD_BF16X3 || y_dt != SFOD_F32) return p;
-  int nb = 0;
-  p = w3_plan_chunked(B, H, W, Cin, Cout, 3, Cout, dt, nb);
-  if (nb != B || !sfod_w3_bn_ok(p, Cin, Cout)) p.ok = 0;      // one sub-batch only: the batch's M is the BatchNorm's
-  return p;
-}
-
 extern "C" int sfod_conv_first_wgrad_bn_supported(int B, int H, int W, int Cin, int Cout, int pool, int dt, int y_dt) {
-  if (g_first_wgrad_fused.get() == 0) return 0;
-  return first_wgrad_bn_plan(B, H, W, Cin, Cout, pool, dt, y_dt).ok ? 1 : 0;
+  if (g_first_wgrad_fused.get() == 0 || pool != 0 || y_dt != SFOD_F32) return 0;
+  return conv_wgrad_plan(B, H, W, Cin, Cout, 3, Cout, dt).first_bn_ok ? 1 : 0;
 }
 
 extern "C" int sfod_conv_first_wgrad_bn(const void* x, const void* dz, const void* y, const float* mean,
@@ -1543,15 +1548,61 @@ extern "C" int sfod_conv_first_wgrad_bn(const void* x, const void* dz, const voi
                "conv_first_wgrad_bn: negative or oversized extent");
   SFOD_REQUIRE(x != nullptr && dz != nullptr && y != nullptr && dw != nullptr, "conv_first_wgrad_bn: null operand");
   SFOD_REQUIRE(mean && invstd && gamma && beta && dgamma && dbeta, "conv_first_wgrad_bn: null BatchNorm argument");
-  const W3Plan p = first_wgrad_bn_plan(B, H, W, Cin, Cout, 0, dt, SFOD_F32);
-  SFOD_REQUIRE(p.ok, "conv_first_wgrad_bn: shape not served (query sfod_conv_first_wgrad_bn_supported)");
+  const ConvWgradPlan p = conv_wgrad_plan(B, H, W, Cin, Cout, 3, Cout, dt);
+  SFOD_REQUIRE(p.first_bn_ok, "conv_first_wgrad_bn: shape not served (query sfod_conv_first_wgrad_bn_supported)");
   SFOD_REQUIRE(ws != nullptr && ws_bytes >= p.ws_bytes, "conv_first_wgrad_bn: workspace too small (sfod_conv_wgrad_ws_bytes)");
   W3BnApply bn;
   bn.dz = (const float*)dz; bn.y = (const float*)y; bn.mean = mean; bn.invstd = invstd; bn.gamma = gamma; bn.beta = beta;
   bn.dgamma = dgamma; bn.dbeta = dbeta;
   // packed: added into, like sfod_conv_wgrad; OIHW: overwritten or added into, like sfod_conv_wgrad_oihw
   const int out_mode = oihw ? (accumulate ? 2 : 1) : 0;
-  return sfod_w3_bn_launch(p, x, bn, dw, ws, B, H, W, out_mode, (hipStream_t)stream);
+  return sfod_w3_bn_launch(p.full, x, bn, dw, ws, B, H, W, out_mode, (hipStream_t)stream);
+}
+
+// WGRAD_GEMM / WGRAD_GEMM_WIDE: one launch over every pixel split, in deterministic mode the slab sum behind it
+static int wgrad_gemm_launch(const ConvWgradPlan& p, const void* x, const void* dy, float* dw, void* ws, int64_t ws_bytes,
+                             int B, int H, int W, int Cin, int Cout, int ksize, int lddy, int dt, hipStream_t s) {
+  SFOD_REQUIRE(p.cpt_shift >= 0, "wgrad3x3: Cin/chunk must be a power of two");
+  if (p.slabs && (ws == nullptr || ws_bytes < p.ws_bytes)) {
+    sfod_set_error("wgrad: deterministic mode needs the workspace of sfod_conv_wgrad_ws_bytes");
+    return SFOD_EBADARG;
+  }
+  const GenWgradPlan& g = p.gen;
+  WgradArgs a;
+  a.M = B * H * W; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ks = ksize; a.lddy = lddy;
+  a.cpt_shift = p.cpt_shift;
+  a.nchunks = ksize * ksize * (Cin / (dt == SFOD_F32 ? 4 : 8));
+  a.Ntot = ksize * ksize * Cin;
+  a.pix_per_split = g.pps;
+  a.tiles_n = g.tiles_n;
+  a.tiles_m = g.tiles_m;
+  // deterministic mode: the splits store into the workspace's slabs, which are then summed into dw in split order
+  a.slab_stride = p.slabs ? (int64_t)Cout * a.Ntot : 0;
+  float* dw_out = p.slabs ? (float*)ws : dw;
+  // the kernel, the name the record gets and the launch shape: one choice (every kernel takes (x, dy, dw, WgradArgs))
+  struct { const void* fn; const char* name; int threads, lds; } k;
+  if (p.kind == WGRAD_GEMM_WIDE) {
+    k = {(const void*)k_conv_wgrad_x3w, "k_conv_wgrad_x3w", 512, 3 * 32 * (128 + 256) * 4};
+    static const hipError_t attr_rc = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
+    SFOD_REQUIRE(attr_rc == hipSuccess, "wgrad: cannot raise the dynamic LDS limit");
+  } else if (dt == SFOD_F32) {
+    k = {(const void*)k_conv_wgrad<float, 2, 2>, "k_conv_wgrad<float,2,2,0>", 256, 2 * 2 * 32 * 512};
+  } else if (dt == SFOD_BF16X3) {
+    k = {(const void*)k_conv_wgrad<bf16_t, 2, 2, true>, "k_conv_wgrad<bf16_t,2,2,1>", 256, 2 * 2 * 64 * 256};
+  } else {
+    k = {(const void*)k_conv_wgrad<bf16_t, 2, 2>, "k_conv_wgrad<bf16_t,2,2,0>", 256, 2 * 2 * 64 * 256};
+  }
+  sfod_note_conv_kernel(k.name);
+  void* args[] = {(void*)&x, (void*)&dy, (void*)&dw_out, (void*)&a};
+  (void)hipLaunchKernel(k.fn, dim3(g.tiles_n * g.tiles_m * g.splits), dim3(k.threads), args, k.lds, s);
+  int rc = sfod_check_launch(p.kind == WGRAD_GEMM_WIDE ? "conv_wgrad_x3w" : "conv_wgrad");
+  if (rc == 0 && p.slabs) {
+    const int64_t n = (int64_t)Cout * a.Ntot;
+    hipLaunchKernelGGL(k_wgrad_slab_sum, dim3(cdiv(n, 1024) > 4096 ? 4096 : cdiv(n, 1024)), dim3(256), 0, s,
+                       (const float*)ws, dw, n, g.splits, a.slab_stride);
+    rc = sfod_check_launch("wgrad_slab_sum");
+  }
+  return rc;
 }
 
 extern "C" int sfod_conv_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int Cin,
@@ -1567,71 +1618,11 @@ extern "C" int sfod_conv_wgrad(const void* x, const void* dy, float* dw, int B, 
   const int E = (dt == SFOD_F32) ? 4 : 8;
   SFOD_REQUIRE(Cin % E == 0 && lddy % E == 0, "wgrad: Cin / lddy must be multiples of the 16-byte chunk (bf16x3: of 8)");
   if ((int64_t)B * H * W == 0) return 0;
-  const int split = (dt == SFOD_BF16X3);
-  SFOD_REQUIRE(!split || Cout % 8 == 0, "wgrad: bf16x3 needs Cout % 8 == 0");
-  {
-    int nb;
-    w3_plan_chunked(B, H, W, Cin, Cout, ksize, lddy, dt, nb);
-    if (nb > 0) return w3_launch_chunked(x, dy, dw, ws, ws_bytes, B, H, W, Cin, Cout, lddy, dt, 0, nb, (hipStream_t)stream);
-  }
+  SFOD_REQUIRE(dt != SFOD_BF16X3 || Cout % 8 == 0, "wgrad: bf16x3 needs Cout % 8 == 0");
+  const ConvWgradPlan p = conv_wgrad_plan(B, H, W, Cin, Cout, ksize, lddy, dt);
   hipStream_t s = (hipStream_t)stream;
-  float* dw_out = dw;
-  WgradArgs a;
-  a.M = B * H * W; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ks = ksize; a.lddy = lddy;
-  const int cpt = Cin / E;
-  a.cpt_shift = 0;
-  if (ksize == 3) {
-    a.cpt_shift = ilog2_exact(cpt);
-    SFOD_REQUIRE(a.cpt_shift >= 0, "wgrad3x3: Cin/chunk must be a power of two");
-  }
-  a.nchunks = ksize * ksize * cpt;
-  a.Ntot = ksize * ksize * Cin;
-  if (a.M == 0) return 0;
-  const GenWgradPlan g = gen_wgrad_plan(a.M, Cout, a.Ntot, dt);
-  a.pix_per_split = g.pps;
-  a.tiles_n = g.tiles_n;
-  a.tiles_m = g.tiles_m;
-  // deterministic mode: every split but a lone one stores into its slab; the slabs are summed into dw in split order
-  a.slab_stride = 0;
-  const bool slabs = sfod_deterministic() && g.splits > 1;
-  if (slabs) {
-    const int64_t need = (int64_t)g.splits * Cout * a.Ntot * 4;
-    if (ws == nullptr || ws_bytes < need) {
-      sfod_set_error("wgrad: deterministic mode needs the workspace of sfod_conv_wgrad_ws_bytes");
-      return SFOD_EBADARG;
-    }
-    a.slab_stride = (int64_t)Cout * a.Ntot;
-    dw_out = (float*)ws;
-  }
-  const int tiles = g.tiles_n * g.tiles_m;
-  if (g.wide) {
-    constexpr int LDS = 3 * 32 * (128 + 256) * 4;
-    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_wgrad_x3w),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    SFOD_REQUIRE(attr_rc == hipSuccess, "wgrad: cannot raise the dynamic LDS limit");
-    sfod_note_conv_kernel("k_conv_wgrad_x3w");
-    hipLaunchKernelGGL(k_conv_wgrad_x3w, dim3(tiles * g.splits), dim3(512), LDS, s, (const bf16_t*)x, (const bf16_t*)dy,
-                       dw_out, a);
-  } else {
-    dim3 grid(tiles * g.splits);
-    sfod_note_conv_kernel(dt == SFOD_F32 ? "k_conv_wgrad<float,2,2,0>"
-                                         : (split ? "k_conv_wgrad<bf16_t,2,2,1>" : "k_conv_wgrad<bf16_t,2,2,0>"));
-    if (dt == SFOD_F32)
-      hipLaunchKernelGGL((k_conv_wgrad<float, 2, 2>), grid, dim3(256), 2 * 2 * 32 * 512, s, (const float*)x,
-                         (const float*)dy, dw_out, a);
-    else if (split)
-      hipLaunchKernelGGL((k_conv_wgrad<bf16_t, 2, 2, true>), grid, dim3(256), 2 * 2 * 64 * 256, s, (const bf16_t*)x,
-                         (const bf16_t*)dy, dw_out, a);
-    else
-      hipLaunchKernelGGL((k_conv_wgrad<bf16_t, 2, 2>), grid, dim3(256), 2 * 2 * 64 * 256, s, (const bf16_t*)x,
-                         (const bf16_t*)dy, dw_out, a);
-  }
-  int rc = sfod_check_launch(g.wide ? "conv_wgrad_x3w" : "conv_wgrad");
-  if (rc == 0 && slabs) {
-    const int64_t n = (int64_t)Cout * a.Ntot;
-    hipLaunchKernelGGL(k_wgrad_slab_sum, dim3(cdiv(n, 1024) > 4096 ? 4096 : cdiv(n, 1024)), dim3(256), 0, s,
-                       (const float*)ws, dw, n, g.splits, a.slab_stride);
-    rc = sfod_check_launch("wgrad_slab_sum");
-  }
-  return rc;
+  if (p.kind == WGRAD_NONE) return 0;       // no channels: dw is empty
+  if (p.kind == WGRAD_PATCH) return wgrad_patch_launch(p, x, dy, dw, ws, ws_bytes, B, H, W, Cin, Cout, lddy, dt, 0, s);
+  return wgrad_gemm_launch(p, x, dy, dw, ws, ws_bytes, B, H, W, Cin, Cout, ksize, lddy, dt, s);
 }
+

@@ -1293,17 +1293,15 @@ int sfod_w3_launch(const W3Plan& p, const void* x, const void* dy, float* dw, vo
   }();
   if (attr_rc != hipSuccess) { sfod_set_error("hipFuncSetAttribute(w3): %s", hipGetErrorString(attr_rc)); return -(int)attr_rc; }
   dim3 grid(p.co_tiles * p.ci_tiles * p.nsplit), blk(512);
-  const int pipe = w3_mode();
-  sfod_note_conv_kernel(split && p.w64 ? "k_wgrad3x3_w64"
-                        : split && pipe ? "k_wgrad3x3_patch<4,1,1>"
-                        : split         ? "k_wgrad3x3_patch<4,1,0>"
-                        : p.CO == 4     ? "k_wgrad3x3_patch<4,0,0>"
-                                        : "k_wgrad3x3_patch<2,0,0>");
-  if (split && p.w64) hipLaunchKernelGGL(k_wgrad3x3_w64, grid, blk, LDS2_TOTAL, s, a);
-  else if (split && pipe) hipLaunchKernelGGL((k_wgrad3x3_patch<4, true, true>), grid, blk, LDS_TOTAL, s, a);
-  else if (split) hipLaunchKernelGGL((k_wgrad3x3_patch<4, true>), grid, blk, LDS_TOTAL, s, a);
-  else if (p.CO == 4) hipLaunchKernelGGL(k_wgrad3x3_patch<4>, grid, blk, LDS_TOTAL, s, a);
-  else hipLaunchKernelGGL(k_wgrad3x3_patch<2>, grid, blk, LDS_TOTAL, s, a);
+  // the kernel, the name the record gets and its LDS size: one choice
+  struct { void (*fn)(W3Args); const char* name; int lds; } k;
+  if (split && p.w64) k = {k_wgrad3x3_w64, "k_wgrad3x3_w64", LDS2_TOTAL};
+  else if (split && w3_mode()) k = {k_wgrad3x3_patch<4, true, true>, "k_wgrad3x3_patch<4,1,1>", LDS_TOTAL};
+  else if (split) k = {k_wgrad3x3_patch<4, true>, "k_wgrad3x3_patch<4,1,0>", LDS_TOTAL};
+  else if (p.CO == 4) k = {k_wgrad3x3_patch<4>, "k_wgrad3x3_patch<4,0,0>", LDS_TOTAL};
+  else k = {k_wgrad3x3_patch<2>, "k_wgrad3x3_patch<2,0,0>", LDS_TOTAL};
+  sfod_note_conv_kernel(k.name);
+  hipLaunchKernelGGL(k.fn, grid, blk, k.lds, s, a);
   int rc = sfod_check_launch("wgrad3x3_patch");
   if (rc) return rc;
   return w3_reduce_launch(p, ws, dw, Cin, Cout, out_mode, s);

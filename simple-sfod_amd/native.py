@@ -275,7 +275,8 @@ def query(name, *args):
 
 
 def set_conv_algo(algo):
-    """0 auto, 1 generic implicit GEMM, 2 halo-patch kernel whenever the shape allows (3x3 bf16)."""
+    """0 auto, 1 generic implicit GEMM, 2 halo-patch kernel whenever the shape allows (3x3 bf16); 3 / 4 auto, but the generic
+    bf16x3 weight gradient always runs its 64 x 64 kernel / its wide 128 x 256 kernel wherever the operands allow it."""
     load().sfod_set_conv_algo(int(algo))
 
 
@@ -814,6 +815,14 @@ def _workspace(dev, nbytes):
     return cur
 
 
+def _wgrad_call(name, args, extents, flops, timer_name=None):
+    """The weight-gradient entry point ``name(*args, ws, ws_bytes)`` with the workspace sfod_conv_wgrad_ws_bytes asks for
+    ``extents`` = (B, H, W, Cin, Cout, ksize, lddy, dt): the largest need of any of its sub-launches, NULL where it is 0."""
+    nbytes = query("sfod_conv_wgrad_ws_bytes", *extents)
+    ws = _workspace(args[0].device, nbytes) if nbytes > 0 else None
+    call(name, *args, ws, nbytes, timer_name=timer_name, flops=flops)
+
+
 def conv_wgrad(x, dy, cout, ksize, dw_packed=None, operand=None):
     """-> fp32 packed grad [Cout, taps, Cin] (accumulated into dw_packed if given).  ``operand``: MFMA operand dtype
     (default: x's); fp32 inputs of a bf16x3 model are converted to pairs here."""
@@ -831,10 +840,8 @@ def conv_wgrad(x, dy, cout, ksize, dw_packed=None, operand=None):
     if dw_packed is None or cout_k != cout:
         assert dw_packed is None, "accumulating bf16x3 weight gradients needs Cout % 8 == 0"
         dw_packed = torch.zeros(cout_k, ksize * ksize, cin, dtype=torch.float32, device=x.device)
-    nbytes = query("sfod_conv_wgrad_ws_bytes", B, H, W, cin, cout_k, ksize, lddy, dt)
-    ws = _workspace(x.device, nbytes) if nbytes > 0 else None
-    call("sfod_conv_wgrad", x, dy, dw_packed, B, H, W, cin, cout_k, ksize, lddy, dt, ws, nbytes,
-         flops=2.0 * B * H * W * cout * ksize * ksize * cin)
+    extents = (B, H, W, cin, cout_k, ksize, lddy, dt)
+    _wgrad_call("sfod_conv_wgrad", (x, dy, dw_packed, *extents), extents, 2.0 * B * H * W * cout * ksize * ksize * cin)
     return dw_packed if cout_k == cout else dw_packed[:cout]
 
 
@@ -853,13 +860,26 @@ def conv_wgrad_oihw(x, dy, dw_oihw, accumulate=False):
     B, H, W, cinp = x.shape
     assert cinp == cin and dw_oihw.is_contiguous() and dw_oihw.dtype == torch.float32
     dy = as_operand(dy, x.dtype)
-    lddy = dy.shape[-1]
-    dt = dt_of(x)
-    nbytes = query("sfod_conv_wgrad_ws_bytes", B, H, W, cin, cout, ksize, lddy, dt)
-    ws = _workspace(x.device, nbytes)
-    call("sfod_conv_wgrad_oihw", x, dy, dw_oihw, B, H, W, cin, cout, ksize, lddy, dt, int(accumulate), ws, nbytes,
-         flops=2.0 * B * H * W * cout * ksize * ksize * cin)
+    extents = (B, H, W, cin, cout, ksize, dy.shape[-1], dt_of(x))
+    _wgrad_call("sfod_conv_wgrad_oihw", (x, dy, dw_oihw, *extents, int(accumulate)), extents,
+                2.0 * B * H * W * cout * ksize * ksize * cin)
     return dw_oihw
+
+
+def _deliver_wgrad(weight, into_sink, packed):
+    """Where a convolution's weight gradient goes: ``into_sink(sink)`` adds it straight into ``grad_sink(weight)`` and says
+    whether it could; otherwise ``packed()`` makes it in the packed layout [Cout, taps, Cin], which is unpacked into the
+    sink (-> None: nothing for autograd to add) or, for a parameter without one, into a new tensor."""
+    sink = grad_sink(weight)
+    if sink is not None and into_sink(sink):
+        return None
+    dwp = packed()
+    if sink is not None:
+        unpack_conv_wgrad(dwp, sink, accumulate=True)
+        return None
+    dw = torch.empty_like(weight)
+    unpack_conv_wgrad(dwp, dw)
+    return dw
 
 
 def conv_weight_grad(x, dy, weight, operand=None):
@@ -869,20 +889,17 @@ def conv_weight_grad(x, dy, weight, operand=None):
     operand = operand or x.dtype
     x, dy = as_operand(x, operand), as_operand(dy, operand)
     cout, cin, k, _ = weight.shape
-    sink = grad_sink(weight)
-    if sink is not None and k == 3 and x.shape[-1] == cin and conv_wgrad_oihw_supported(x, dy, cout, 3):
-        conv_wgrad_oihw(x, dy, sink, accumulate=True)     # the slab reduction writes OIHW directly
-        return None
-    if sink is not None and k == 1 and x.shape[-1] == cin and (dt_of(x) != BF16X3 or cout % 8 == 0):
-        conv_wgrad(x, dy, cout, 1, dw_packed=sink.view(cout, 1, cin))    # packed [Cout,1,Cin] IS the OIHW layout: the
-        return None                                                     # kernel's atomics accumulate in place
-    dwp = conv_wgrad(x, dy, cout, k)
-    if sink is not None:
-        unpack_conv_wgrad(dwp, sink, accumulate=True)
-        return None
-    dw = torch.empty_like(weight)
-    unpack_conv_wgrad(dwp, dw)
-    return dw
+
+    def into_sink(sink):
+        if k == 3 and x.shape[-1] == cin and conv_wgrad_oihw_supported(x, dy, cout, 3):
+            conv_wgrad_oihw(x, dy, sink, accumulate=True)     # the slab reduction writes OIHW directly
+            return True
+        if k == 1 and x.shape[-1] == cin and (dt_of(x) != BF16X3 or cout % 8 == 0):
+            conv_wgrad(x, dy, cout, 1, dw_packed=sink.view(cout, 1, cin))    # packed [Cout,1,Cin] IS the OIHW layout: the
+            return True                                                     # kernel's atomics accumulate in place
+        return False
+
+    return _deliver_wgrad(weight, into_sink, lambda: conv_wgrad(x, dy, cout, k))
 
 
 def set_first_wgrad_fused(on):
@@ -912,11 +929,9 @@ def conv_first_wgrad_bn(x, dz, y, mean, invstd, gamma, beta, dgamma, dbeta, dw, 
     assert dw.is_contiguous() and dw.dtype == torch.float32
     assert dz.dtype == torch.float32 and y.dtype == torch.float32 and dz.shape == y.shape == (B, H, W, cout)
     dt = dt_of(x)
-    nbytes = query("sfod_conv_wgrad_ws_bytes", B, H, W, cin, cout, 3, cout, dt)
-    ws = _workspace(x.device, nbytes)
-    call("sfod_conv_first_wgrad_bn", x, dz, y, mean, invstd, gamma, beta, dgamma, dbeta, dw, B, H, W, cin, cout, dt,
-         int(oihw), int(accumulate), ws, nbytes, timer_name="sfod_conv_wgrad_oihw" if oihw else "sfod_conv_wgrad",
-         flops=2.0 * B * H * W * cout * 9 * cin)
+    _wgrad_call("sfod_conv_first_wgrad_bn", (x, dz, y, mean, invstd, gamma, beta, dgamma, dbeta, dw, B, H, W, cin, cout, dt,
+                                             int(oihw), int(accumulate)), (B, H, W, cin, cout, 3, cout, dt),
+                2.0 * B * H * W * cout * 9 * cin, timer_name="sfod_conv_wgrad_oihw" if oihw else "sfod_conv_wgrad")
     return dw
 
 
@@ -924,19 +939,13 @@ def conv_first_weight_grad(x, dz, y, mean, invstd, gamma, beta, dgamma, dbeta, w
     """``conv_weight_grad(x, dy, weight)`` of the first layer with dy formed inside the kernel (``conv_first_wgrad_bn``): the
     same route into ``grad_sink(weight)`` / a new tensor, so the same bits."""
     cout, cin, _, _ = weight.shape
-    sink = grad_sink(weight)
     args = (x, dz, y, mean, invstd, gamma, beta, dgamma, dbeta)
-    if sink is not None and x.shape[-1] == cin:
-        conv_first_wgrad_bn(*args, sink, accumulate=True)
-        return None
-    dwp = torch.zeros(cout, 9, x.shape[-1], dtype=torch.float32, device=x.device)
-    conv_first_wgrad_bn(*args, dwp)
-    if sink is not None:
-        unpack_conv_wgrad(dwp, sink, accumulate=True)
-        return None
-    dw = torch.empty_like(weight)
-    unpack_conv_wgrad(dwp, dw)
-    return dw
+
+    def into_sink(sink):
+        return x.shape[-1] == cin and conv_first_wgrad_bn(*args, sink, accumulate=True) is sink
+
+    return _deliver_wgrad(weight, into_sink, lambda: conv_first_wgrad_bn(
+        *args, torch.zeros(cout, 9, x.shape[-1], dtype=torch.float32, device=x.device)))
 
 
 def bias_grad(dy, n, db=None, accumulate=False):

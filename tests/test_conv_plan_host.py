@@ -50,6 +50,49 @@ def test_queries_reproduce_the_recorded_plans(lib, dump):
     assert lib.sfod_last_error() == err_before          # a query reports nothing, hostile extents included
 
 
+def test_wgrad_queries_reproduce_the_recorded_plans(lib, dump):
+    """tests/golden/conv_wgrad_plans.txt: every 4871st row of tools/dump_conv_plans.py --wgrad (and every hostile and CHUNKED
+    row), as the library answered before the three weight-gradient queries became readers of one plan.  (The 24 hostile
+    rows with no input channels, no output channels or ksize 0 are recorded as "0 0 0": that library divided by zero on
+    them.)  Each row is asked again from its own extents and reproduces the recorded text -- but for a batch that the
+    halo-patch kernel walks in sub-batches: there sfod_conv_wgrad_ws_bytes is the largest need of any sub-batch, where the
+    recording has the first one's, which a smaller remainder can exceed."""
+    with open(os.path.join(HERE, "golden", "conv_wgrad_plans.txt")) as f:
+        table = [line.rstrip("\n") for line in f]
+    assert len(table) >= 1000
+    answers = [tuple(int(v) for v in r.split(" : ")[1].split()) for r in table]
+    dets = [int(r.split()[2]) for r in table]
+    assert (0, 0, 0) in answers                                                    # not served / nothing to do
+    assert any(ws > 0 and oihw == 1 for ws, oihw, _ in answers)                    # halo patch
+    assert any(ws > 0 and oihw == 0 and det for (ws, oihw, _), det in zip(answers, dets))      # deterministic slabs
+    assert not any(ws > 0 and oihw == 0 and not det for (ws, oihw, _), det in zip(answers, dets))
+    assert {a[1] for a in answers} == {0, 1} and {a[2] for a in answers} == {0, 1}
+    chunked = {c[:5]: c[5] for c in dump.CHUNKED}
+    wrong, moved, err_before = [], set(), lib.sfod_last_error()
+    det_before = lib.sfod_get_deterministic()
+    try:
+        for row in table:
+            asked, want = row.split(" : ")
+            algo, pipe, det, *e = (int(v) for v in asked.split())
+            dump.wgrad_set(lib, algo, pipe, det)
+            got = dump.wgrad_answers(lib, *e)
+            subs = chunked.get(tuple(e[:5])) if e[5:] == [3, e[4], dump.BF16X3] else None
+            if subs and got.split()[1] == "1":
+                B, H, W, cin, cout, ks, lddy, dt = e
+                need = max(lib.sfod_conv_wgrad_ws_bytes(n, H, W, cin, cout, ks, lddy, dt) for n in subs)
+                if got.split()[1:] != want.split()[1:] or int(got.split()[0]) != need:
+                    wrong.append((asked, want, got, need))
+                if got != want:
+                    moved.add(tuple(e[:5]))
+            elif got != want:
+                wrong.append((asked, want, got))
+    finally:
+        dump.wgrad_set(lib, 0, 2, det_before)
+    assert not wrong, wrong[:10]
+    assert moved >= set(c[:5] for c in dump.CHUNKED[:4]), moved       # the four whose remainder wants more than a full sub-batch
+    assert lib.sfod_last_error() == err_before          # a query reports nothing, hostile extents included
+
+
 def _first_layer_launch(lib, stats, buffers):
     """sfod_conv_fwd_scratch on 1 x 64 x 64, 8 -> 64, 3x3: bf16 operands but an fp32 output"""
     x, w, y = buffers
