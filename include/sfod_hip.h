@@ -359,6 +359,34 @@ int sfod_bn_relu_pool_bwd(const void* dz, const void* y, const float* mean, cons
  * `ws` must then have SFOD_BN_BWD_SCRATCH_ROWS more rows of 2 * C floats behind them (scratch of the two-stage sum). */
 #define SFOD_BN_BWD_SCRATCH_ROWS 32
 int sfod_bn_bwd_ws_floats(int M, int C);
+/* ---- GroupNorm + ReLU of the box head's convolutions (MODEL.ROI_BOX_HEAD.NORM "GN": d2 get_norm -> torch.nn.GroupNorm(32,
+ * CONV_DIM), eps 1e-5, behind every conv of FastRCNNConvFCHead) on ROI tensors [R, PP, C], NHWC.  Statistics are per (ROI,
+ * group) over the n = PP * C / groups elements of the group, in fp32: the mean first (sum / n), then the centred sum of
+ * squares (var = sum (y - mean)^2 / n, biased); rstd = 1 / sqrt(var + eps).  E[y^2] - E[y]^2 is never formed.
+ *   z = relu(((y - mean_g) * rstd_g) * gamma_c + beta_c)      (the last two as one fused multiply-add; relu = fmaxf(., 0))
+ * y: the convolution's output, y_dt SFOD_F32 or SFOD_BF16.  z: z_dt = y_dt, or SFOD_BF16X3 / SFOD_F16X3 from an fp32 y (the
+ * next layer's operand, written directly); z_grad_operand (may be NULL; z_dt SFOD_F16X3 only): the same values once more as
+ * SFOD_BF16X3 pairs, that layer's weight-gradient operand (the producer-writes-both convention of sfod_bn_relu_pool_fwd2).
+ * mean, rstd: fp32 [R, groups], saved for the backward.  An all-zero (padding) ROI gives exactly relu(beta), as does any
+ * group of one element.  relu 0 / 1.  C <= 1024, C % groups == 0, C % 8 == 0 (fp32 z: C % 4 == 0); R == 0: no launch.
+ * Held per element to DESIGN.md 4.7's bound (tests/helpers/box_head_definitions.py gn_forward_bound). */
+int sfod_group_norm_relu_fwd(const void* y, const float* gamma, const float* beta, void* z, void* z_grad_operand,
+                             float* mean, float* rstd, int R, int PP, int C, int groups, float eps, int relu, int y_dt,
+                             int z_dt, void* stream);
+/* backward: dz the gradient of z, y / mean / rstd as the forward saw and saved them.  The ReLU gate is RECOMPUTED from y
+ * (the forward's own pre-activation expression, bit for bit: gate = pre-activation > 0), z is not needed.  With
+ * gz = dz * gate, g = gz * gamma_c, xhat = (y - mean_g) * rstd_g and mean_grp the mean over the group's n elements:
+ *   dy = rstd_g * (g - mean_grp(g) - xhat * mean_grp(g * xhat)),  dbeta_c = sum_{r,p} gz,  dgamma_c = sum_{r,p} gz * xhat.
+ * dz, y: dt SFOD_F32 or SFOD_BF16; dy: dy_dt = dt, or SFOD_BF16X3 from fp32 (the operand of the backward products).
+ * dgamma / dbeta: every workgroup writes the sums of its ROIs (taken in ROI order) to its row of ws
+ * (sfod_group_norm_bwd_ws_floats(R, C) floats), a second launch adds the rows in row order: no atomics, the same bits on
+ * every run; accumulate 1 adds the result into dgamma / dbeta (a parameter's gradient accumulator) instead of storing it.
+ * A ROI whose dz is zero (a padding row) adds nothing and gets dy = 0.  R == 0: no kernel (dgamma = dbeta = 0 unless
+ * accumulating). */
+int sfod_group_norm_relu_bwd(const void* dz, const void* y, const float* mean, const float* rstd, const float* gamma,
+                             const float* beta, void* dy, float* dgamma, float* dbeta, float* ws, int R, int PP, int C,
+                             int groups, int relu, int accumulate, int dt, int dy_dt, void* stream);
+int64_t sfod_group_norm_bwd_ws_floats(int R, int C);
 /* ---- ResNet-101-C4 backbone helpers (d2 build_resnet_backbone selected by the r101 yaml's missing
  * BACKBONE.NAME, configs/r101_c4_cs_foggy_adaptive_teacher_source_free.yaml:1-28) ----
  * The pointwise kernels below (add_act, subsample2, maxpool3s2, act_bwd, add_inplace, add_act_bwd, mul_mask) are each ONE

@@ -219,11 +219,12 @@ def get_cfg():
     _C.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION = 14
     _C.MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO = 0
     _C.MODEL.ROI_BOX_HEAD.POOLER_TYPE = "ROIAlignV2"
-    _C.MODEL.ROI_BOX_HEAD.NUM_FC = 0
-    _C.MODEL.ROI_BOX_HEAD.FC_DIM = 1024
-    _C.MODEL.ROI_BOX_HEAD.NUM_CONV = 0
-    _C.MODEL.ROI_BOX_HEAD.CONV_DIM = 256
-    _C.MODEL.ROI_BOX_HEAD.NORM = ""
+    # d2's FastRCNNConvFCHead (modeling/box_head_options.py; the named yamls set NUM_FC 2 and leave the rest).  Built:
+    _C.MODEL.ROI_BOX_HEAD.NUM_FC = 0          # linear layers + ReLU after the flatten: an integer in [0, 4]
+    _C.MODEL.ROI_BOX_HEAD.FC_DIM = 1024       # their width: a positive multiple of 8
+    _C.MODEL.ROI_BOX_HEAD.NUM_CONV = 0        # 3x3 convolutions (pad 1) + [norm] + ReLU: an integer in [0, 4]; NUM_CONV + NUM_FC >= 1
+    _C.MODEL.ROI_BOX_HEAD.CONV_DIM = 256      # their width: 8 x a power of two, <= 1024 (>= 32 under NORM "GN")
+    _C.MODEL.ROI_BOX_HEAD.NORM = ""           # "" or "GN" = GroupNorm(32, CONV_DIM), eps 1e-5, conv bias off; BN / SyncBN / LN raise
     _C.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG = False
     _C.MODEL.ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES = False
     _C.MODEL.RESNETS = CN()

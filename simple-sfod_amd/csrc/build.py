@@ -19,6 +19,7 @@ SOURCES = {
     "detect.hip": ["-ffp-contract=off"],
     "roi_align.hip": ["-ffp-contract=off"],
     "elementwise.hip": [],
+    "group_norm.hip": [],
     "gemm_conv.hip": [],
     "conv3x3_patch.hip": [],
     "wgrad3x3_patch.hip": [],

@@ -9,8 +9,9 @@ domain branch is not executed.  Forward passes run on the HIP conv / GEMM kernel
 discriminator also has a hand-written backward (``dc_img_loss``: BCE-with-logits against a constant
 domain label, ``source_free_adaptive_teacher_rcnn.py:145-155``), so ``DOMAIN_CLASSIFIER.IMAGE: True``
 trains; the instance-level head has one too (``dc_ins_loss``: ROIAlign -> box head -> GRL -> DAInsHead with
-dropout -> BCE, ``source_free_adaptive_teacher_rcnn.py:157-201,341-349``), gradients reach the box head and,
-through ROIAlign, the backbone.
+dropout -> BCE, ``source_free_adaptive_teacher_rcnn.py:157-201,341-349``), gradients reach the box head (any built head
+with NUM_FC >= 1: its parameter gradients come back as a list in ``box_head.parameters()`` order) and, through ROIAlign, the
+backbone.
 """
 import torch
 import torch.nn as nn
@@ -164,7 +165,8 @@ class _DCInsLossFn(torch.autograd.Function):
         fc1 = getattr(head, head.da_ins_fc1_layers[0])
         fc2 = getattr(head, head.da_ins_fc2_layers[0])
         fc3 = getattr(head, head.da_ins_fc3_layers[0])
-        r1 = native.conv_fwd(st["h2"], native.pack_fc_weight(fc1.weight.detach(), dt), fc1.bias.detach(), 1024, 1, act=1)
+        bf = heads.box_features(st)
+        r1 = native.conv_fwd(bf, native.pack_fc_weight(fc1.weight.detach(), dt), fc1.bias.detach(), 1024, 1, act=1)
         z1 = r1
         if masks is not None:
             z1 = native.mul_mask_(r1.clone(), masks[0], 2.0)
@@ -214,15 +216,15 @@ class _DCInsLossFn(torch.autograd.Function):
             native.mul_mask_(d1, masks[0], 2.0)
         native.act_bwd_(d1, r1, 1)
         # fc1
-        dw1 = native.conv_wgrad(st["h2"], d1, 1024, 1, operand=dtype).view(1024, -1)
+        dw1 = native.conv_wgrad(heads.box_features(st), d1, 1024, 1, operand=dtype).view(1024, -1)
         db1 = native.bias_grad(d1, 1024)
         dh2 = native.conv_fwd(d1, native.pack_fc_weight(fc1.weight.detach(), dt, transpose=True), None,
                               fc1.in_features, 1)
         # gradient reversal (gradient_scalar(box_features, -1.0)), then the box head and ROIAlign
         dh2 = dh2 * -1.0
-        dfeat, (bw1, bb1, bw2, bb2) = heads._box_head_backward(st, rois, dh2)
+        dfeat, head_grads = heads._box_head_backward(st, rois, dh2)      # in box_head.parameters() order, like ``params`` below
         ctx.st = ctx.acts = None
-        return (None, None, dfeat, None, None, None, bw1, bb1, bw2, bb2, dw1, db1, dw2, db2, dw3, db3)
+        return (None, None, dfeat, None, None, None, *head_grads, dw1, db1, dw2, db2, dw3, db3)
 
 
 def dc_ins_loss(roi_heads, head, feat_nchw, rois, domain_label, training=True):
@@ -235,6 +237,6 @@ def dc_ins_loss(roi_heads, head, feat_nchw, rois, domain_label, training=True):
     if training:
         R = rois.shape[0]
         masks = [(torch.rand(R, 1024, device=rois.device) >= 0.5).to(torch.uint8) for _ in range(2)]
-    params = [bh.fc1.weight, bh.fc1.bias, bh.fc2.weight, bh.fc2.bias,
+    params = list(bh.parameters()) + [
               fc[0].weight, fc[0].bias, fc[1].weight, fc[1].bias, fc[2].weight, fc[2].bias]
     return _DCInsLossFn.apply(roi_heads, head, feat_nchw, rois, float(domain_label), masks, *params)

@@ -20,6 +20,7 @@ from .. import native
 from ..registry import BACKBONE_REGISTRY, META_ARCH_REGISTRY, PROPOSAL_GENERATOR_REGISTRY, ROI_HEADS_REGISTRY
 from ..structures import Boxes, ImageList, Instances
 from .batched import BatchedGT, gather_gt
+from .box_head_options import validate_box_head_cfg
 from .dann import DAInsHead, FCDiscriminator_img, dc_img_loss, dc_ins_loss
 
 
@@ -160,6 +161,8 @@ class SourceFreeAdaptiveTeacherGeneralizedRCNN(GeneralizedRCNN):
         self.DC_img = FCDiscriminator_img(self.backbone._out_feature_channels[self.dis_type],
                                           compute_dtype=self.compute_dtype)
         self.ins_dc = cfg.SEMISUPNET.INS_DC
+        if hasattr(getattr(self.roi_heads, "box_head", None), "options"):
+            validate_box_head_cfg(cfg)      # NUM_FC 0 cannot feed the instance-level branch: a ValueError naming the keys
         if self.ins_dc:
             self.DC_ins = DAInsHead(self.roi_heads.box_predictor.cls_score.in_features, [self.dis_type],
                                     compute_dtype=self.compute_dtype)

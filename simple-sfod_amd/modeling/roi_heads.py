@@ -7,9 +7,11 @@ Mirrors ``/root/reference/daod/modeling/roi_heads/source_free_adaptive_teacher_r
 ``label_and_sample_proposals`` ``:165-215``; and the Detectron2 pieces it inherits (SURVEY.md
 A.11-A.13): add_ground_truth_to_proposals, Matcher [0.5], subsample 512 @ 0.25, ROIAlignV2 7x7 (POOLER_TYPE,
 POOLER_SAMPLING_RATIO and POOLER_RESOLUTION <= 16 are built: modeling/roi_pooler.py),
-FastRCNNConvFCHead (2 FC), FastRCNNOutputLayers losses / inference.
+FastRCNNConvFCHead (NUM_CONV / CONV_DIM / NUM_FC / FC_DIM / NORM "" or "GN" are built: modeling/box_head_options.py; the named
+yamls' 2-FC head keeps its own pass), FastRCNNOutputLayers losses / inference.
 
-State-dict keys: ``roi_heads.box_head.fc{1,2}.*``, ``roi_heads.box_predictor.{cls_score,bbox_pred}.*``.
+State-dict keys: ``roi_heads.box_head.{conv{k}.{weight,bias}, conv{k}.norm.{weight,bias}, fc{k}.{weight,bias}}`` (Detectron2's),
+``roi_heads.box_predictor.{cls_score,bbox_pred}.*``.
 """
 import math
 
@@ -21,6 +23,7 @@ from ..registry import ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY
 from ..structures import Boxes, Instances, ShapeSpec
 from .offchain import OffChain as _OffChain, heads_on as _heads_on
 from .batched import BatchedDetections, BatchedGT, BatchedProposals
+from .box_head_options import GN_EPS, GN_GROUPS, box_head_options
 from .box_regression import ROI_DEFAULT_WEIGHTS, roi_box_reg_options
 from .proposal_options import roi_iou_band
 from .roi_pooler import roi_pooler_options
@@ -49,34 +52,48 @@ class ROIPooler(nn.Module):
 
 @ROI_BOX_HEAD_REGISTRY.register()
 class FastRCNNConvFCHead(nn.Module):
-    """NUM_CONV 0 + NUM_FC fully connected layers with ReLU (c2_xavier_fill)."""
+    """Detectron2's FastRCNNConvFCHead: NUM_CONV x (conv3x3 pad 1, ``bias = not norm``, [GroupNorm(32) at ``conv{k}.norm``],
+    ReLU; c2_msra_fill), flatten in (C, H, W) order, NUM_FC x (linear, ReLU; c2_xavier_fill).  What is built, and the
+    ValueErrors for the rest: modeling/box_head_options.py."""
 
     def __init__(self, cfg, input_shape):
         super().__init__()
-        assert cfg.MODEL.ROI_BOX_HEAD.NUM_CONV == 0, "conv layers in the box head are not on the hot path"
-        num_fc, fc_dim = cfg.MODEL.ROI_BOX_HEAD.NUM_FC, cfg.MODEL.ROI_BOX_HEAD.FC_DIM
-        assert num_fc == 2, "the named configs use NUM_FC 2"
-        self._in = input_shape.channels * input_shape.height * input_shape.width
+        self.options = o = box_head_options(cfg)
+        c, h, w = input_shape.channels, input_shape.height, input_shape.width
+        self.convs = []
+        for k in range(o.num_conv):
+            conv = nn.Conv2d(c, o.conv_dim, kernel_size=3, padding=1, bias=not o.norm)
+            nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+            if conv.bias is not None:
+                nn.init.constant_(conv.bias, 0)
+            if o.norm:
+                conv.norm = nn.GroupNorm(GN_GROUPS, o.conv_dim, eps=GN_EPS)      # d2 get_norm("GN"): weight 1, bias 0
+            self.add_module("conv{}".format(k + 1), conv)
+            self.convs.append(conv)
+            c = o.conv_dim
+        self._in = c * h * w
         self.fcs = []
         d = self._in
-        for k in range(num_fc):
-            fc = nn.Linear(d, fc_dim)
+        for k in range(o.num_fc):
+            fc = nn.Linear(d, o.fc_dim)
             nn.init.kaiming_uniform_(fc.weight, a=1)
             nn.init.constant_(fc.bias, 0)
             self.add_module("fc{}".format(k + 1), fc)
             self.fcs.append(fc)
-            d = fc_dim
+            d = o.fc_dim
         self._out = d
+        # channels only behind an FC; else the last convolution's (C, H, W) map, flattened by the predictor in that order
+        self._out_shape = ShapeSpec(channels=d) if o.num_fc else ShapeSpec(channels=c, height=h, width=w)
 
     @property
     def output_shape(self):
-        return ShapeSpec(channels=self._out)
+        return self._out_shape
 
 
 class FastRCNNOutputLayers(nn.Module):
     def __init__(self, cfg, input_shape):
         super().__init__()
-        d = input_shape.channels
+        d = input_shape.channels * (input_shape.height or 1) * (input_shape.width or 1)      # d2: a (C, H, W) input is flattened
         self.num_classes = cfg.MODEL.ROI_HEADS.NUM_CLASSES
         # BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA / BBOX_REG_WEIGHTS / CLS_AGNOSTIC_BBOX_REG / BBOX_REG_LOSS_WEIGHT (ValueError
         # naming the key for what is not built); ``_box_reg`` is what the native calls take: None = the default entry points
@@ -279,6 +296,9 @@ class StandardROIHeads(nn.Module):
         self.box_predictor = self._make_predictor(cfg, self.box_head.output_shape)
         self.pooled = res
         self.channels = shape.channels
+        # the named yamls' 2-FC head runs the pass written for it below; every other built head the general one
+        opts = getattr(self.box_head, "options", None)
+        self._general = opts is not None and not opts.is_default()
         self.compute_dtype = native.mode_dtype(cfg.SFOD.COMPUTE_DTYPE)
         K = self.num_classes
         self.pred_cols = self.box_predictor.box_reg.pred_cols(K)      # K + 1 scores | 4K deltas (class-agnostic: 4)
@@ -292,6 +312,8 @@ class StandardROIHeads(nn.Module):
 
     def _params(self):
         bh, bp = self.box_head, self.box_predictor
+        if self._general:      # the head's parameters in module order, then the predictor's
+            return list(bh.parameters()) + [bp.cls_score.weight, bp.cls_score.bias, bp.bbox_pred.weight, bp.bbox_pred.bias]
         return [bh.fc1.weight, bh.fc1.bias, bh.fc2.weight, bh.fc2.bias, bp.cls_score.weight, bp.cls_score.bias,
                 bp.bbox_pred.weight, bp.bbox_pred.bias]
 
@@ -303,6 +325,8 @@ class StandardROIHeads(nn.Module):
         that otherwise sit between the pseudo labels and the losses).  The trainer calls it (``model.prefetch_features``)
         while the teacher is still labelling; nothing changes the weights before this step's update, and what is not
         taken by then is dropped at the start of the next step (``drop_prefetched``)."""
+        if self._general:      # nothing is packed ahead for the other heads: their pass packs where it multiplies
+            return
         dt = native.dt_of_dtype(self.compute_dtype)
         gdt = native.dt_of_dtype(native.grad_dtype_of(self.compute_dtype))
         bh, bp, C = self.box_head, self.box_predictor, self.channels
@@ -318,6 +342,8 @@ class StandardROIHeads(nn.Module):
 
     # ---- box branch: ROIAlign -> fc1 -> fc2 -> fused (cls_score | bbox_pred) -------------------------
     def _box_forward(self, feat_nchw, rois):
+        if self._general:
+            return self._box_forward_general(feat_nchw, rois)
         dtype = self.compute_dtype
         dt = native.dt_of_dtype(dtype)
         feat = native.nhwc_operand(feat_nchw, dtype)
@@ -342,6 +368,8 @@ class StandardROIHeads(nn.Module):
         return st
 
     def _box_backward(self, st, rois, d_pred, feat_shape_nchw):
+        if self._general:
+            return self._box_backward_general(st, rois, d_pred)
         dtype = native.grad_dtype_of(self.compute_dtype)      # operands of the backward products ("f16x3": bf16 pairs)
         dt = native.dt_of_dtype(dtype)
         bh = self.box_head
@@ -364,7 +392,10 @@ class StandardROIHeads(nn.Module):
 
     def _box_head_backward(self, st, rois, dh2):
         """grad wrt the box-head output (``box_features`` = relu(fc2), consumed in place) -> (grad wrt the feature
-        map as an NCHW view, [dw1, db1, dw2, db2]); dw1 is None when it went straight into the flat gradient."""
+        map as an NCHW view, the head's parameter gradients as a list in ``_params()`` order: [dw1, db1, dw2, db2]); an entry is
+        None when it went straight into the flat gradient (dw1)."""
+        if self._general:
+            return self._box_head_backward_general(st, rois, dh2)
         dtype = native.grad_dtype_of(self.compute_dtype)      # operands of the backward products ("f16x3": bf16 pairs)
         dt = native.dt_of_dtype(dtype)
         bh = self.box_head
@@ -404,6 +435,142 @@ class StandardROIHeads(nn.Module):
                                      self.box_pooler.scale, **self.box_pooler.options)
         off.join(dw1, db1, dw2, db2)     # the heads' gradients are final before anyone (all-reduce, SGD, autograd) reads them
         return dfeat.permute(0, 3, 1, 2), [dw1, db1, dw2, db2]
+
+    def box_features(self, st):
+        """the box head's output of a pass's state (``box_features`` of the reference: what the instance-level domain
+        discriminator reads), [R, FC_DIM]"""
+        if not self._general:
+            return st["h2"]
+        if not st["hs"]:
+            raise ValueError("MODEL.ROI_BOX_HEAD.NUM_FC 0: the box head has no flat FC features (SEMISUPNET.INS_DC / "
+                             "DOMAIN_CLASSIFIER.INSTANCE need NUM_FC >= 1)")
+        return st["hs"][-1]
+
+    # ---- the general pass: ROIAlign -> NUM_CONV x (conv3x3 [+ GroupNorm] + ReLU) -> NUM_FC x (linear + ReLU) -> predictor ----
+    def _box_forward_general(self, feat_nchw, rois):
+        dtype = self.compute_dtype
+        dt = native.dt_of_dtype(dtype)
+        feat = native.nhwc_operand(feat_nchw, dtype)
+        bh, bp, P = self.box_head, self.box_predictor, self.pooled
+        pooled = native.roi_align_fwd(feat, rois, P, self.box_pooler.scale, **self.box_pooler.options)
+        R = pooled.shape[0]
+        x = pooled.view(R, P, P, self.channels)
+        xw = x                                     # what the next layer's weight gradient reads (converted there if need be)
+        convs = []
+        for conv in bh.convs:
+            # (a backbone width the 3x3 kernels do not take -- not 8 x a power of two -- gets zero channels behind; CONV_DIM is
+            # held to such a width by box_head_options, so only the first layer's input can need it)
+            cp = native.conv3x3_channels(x.shape[-1], dt)
+            same = xw is x
+            x = native.pad_channels(x, cp)
+            xw = x if same else native.pad_channels(xw, cp)
+            w = native.pack_conv_weight(conv.weight.detach(), cp, dt)
+            norm = getattr(conv, "norm", None)
+            if norm is not None:
+                y = native.conv_fwd(x, w, None, conv.out_channels, 3, act=0)
+                z, zg, mean, rstd = native.group_norm_relu_fwd(y, norm.weight.detach(), norm.bias.detach(), norm.num_groups,
+                                                               norm.eps, out_dtype=dtype, with_grad_operand=True)
+                convs.append({"xw": xw, "y": y, "mean": mean, "rstd": rstd})
+                x, xw = z, zg
+            else:
+                y = native.conv_fwd(x, w, conv.bias.detach(), conv.out_channels, 3, act=1)
+                convs.append({"xw": xw, "y": y})
+                x = xw = y
+        chw = x.shape[-1]                          # (c, p) state-dict order of the first flat layer <-> (p, c) in the kernels
+        flat = x.view(R, -1)
+        h, hs = flat, []
+        for i, fc in enumerate(bh.fcs):
+            w = native.pack_fc_weight(fc.weight.detach(), dt, chw_c=chw if i == 0 else 0)
+            h = native.conv_fwd(h, w, fc.bias.detach(), fc.out_features, 1, act=1)
+            hs.append(h)
+        wp = torch.cat([bp.cls_score.weight.detach(), bp.bbox_pred.weight.detach()])
+        bpb = torch.cat([bp.cls_score.bias.detach(), bp.bbox_pred.bias.detach()])
+        wpp = native.pack_fc_weight(wp, dt, chw_c=0 if hs else chw)
+        pred = native.conv_fwd(h, wpp, bpb, wp.shape[0], 1, out_dtype=torch.float32, ldy=self.pred_ld)
+        return {"x0": pooled.view(R, -1), "convs": convs, "flat": xw.view(R, -1), "chw": chw, "hs": hs, "pred": pred, "wp": wp,
+                "feat_shape": tuple(feat.shape)}
+
+    def _box_backward_general(self, st, rois, d_pred):
+        dtype = native.grad_dtype_of(self.compute_dtype)
+        dt = native.dt_of_dtype(dtype)
+        K, NP = self.num_classes, self.pred_cols
+        h = st["hs"][-1] if st["hs"] else st["flat"]
+        chw = 0 if st["hs"] else st["chw"]
+        d_pred_c = native.cast(d_pred, dtype)
+        off = _OffChain(_heads_on(d_pred))
+
+        def pred_grads():
+            dwp = native.conv_wgrad(h, d_pred_c, NP, 1, operand=dtype).view(NP, -1)
+            if chw:      # the predictor reads the (C, H, W) map: back to the state dict's (c, p) order
+                dw = torch.empty(NP, dwp.shape[1], dtype=torch.float32, device=dwp.device)
+                native.unpack_fc_wgrad(dwp, dw, chw_c=chw)
+                dwp = dw
+            return dwp, native.bias_grad(d_pred, NP)
+
+        dwp, dbp = off.run(pred_grads, h, d_pred_c, d_pred)
+        wpt = native.pack_fc_weight(st["wp"], dt, chw_c=chw, transpose=True, ld=self.pred_ld)
+        dh = native.conv_fwd(d_pred_c, wpt, None, st["wp"].shape[1], 1)
+        dfeat, hg = self._box_head_backward_general(st, rois, dh)     # (joins the side stream)
+        off.join(dwp, dbp)
+        return dfeat, hg + [dwp[: K + 1].contiguous(), dbp[: K + 1].contiguous(), dwp[K + 1:].contiguous(),
+                            dbp[K + 1:].contiguous()]
+
+    def _box_head_backward_general(self, st, rois, dh):
+        """``_box_head_backward`` of any built head: the layers in reverse; weight, bias and GroupNorm-parameter gradients in
+        ``box_head.parameters()`` order (None: added straight into the parameter's ``grad_sink``).  The weight and bias
+        gradients run beside the data-gradient path; the GroupNorm backward is ON that path (it makes the convolution's dy)
+        and sums dgamma / dbeta in a fixed order (include/sfod_hip.h), so the pass is reproducible bit for bit under
+        SFOD.DETERMINISTIC."""
+        dtype = native.grad_dtype_of(self.compute_dtype)
+        dt = native.dt_of_dtype(dtype)
+        bh, P = self.box_head, self.pooled
+        off = _OffChain(_heads_on(dh))
+        grads = {}
+        d = dh
+        for i in reversed(range(len(bh.fcs))):
+            fc, xin, chw = bh.fcs[i], (st["hs"][i - 1] if i else st["flat"]), (0 if i else st["chw"])
+            native.act_bwd_(d, st["hs"][i], 1)
+
+            def fc_param_grads(fc=fc, xin=xin, d=d, chw=chw):
+                dw = native.conv_wgrad(xin, d, fc.out_features, 1, operand=dtype).view(fc.out_features, -1)
+                if chw:
+                    dwp, dw = dw, native.grad_sink(fc.weight)
+                    if dw is not None:
+                        native.unpack_fc_wgrad(dwp, dw, chw_c=chw, accumulate=True)
+                        dw = None
+                    else:
+                        dw = torch.empty_like(fc.weight)
+                        native.unpack_fc_wgrad(dwp, dw, chw_c=chw)
+                return dw, native.bias_grad(d, fc.out_features)
+
+            grads[fc.weight], grads[fc.bias] = off.run(fc_param_grads, xin, d)
+            wt = native.pack_fc_weight(fc.weight.detach(), dt, chw_c=chw, transpose=True)
+            d = native.conv_fwd(d, wt, None, fc.in_features, 1)
+        for k in reversed(range(len(bh.convs))):
+            conv, rec = bh.convs[k], st["convs"][k]
+            d = d.view(rec["y"].shape)
+            norm = getattr(conv, "norm", None)
+            if norm is not None:
+                gs, bs = native.grad_sink(norm.weight), native.grad_sink(norm.bias)
+                into = gs is not None and bs is not None
+                dy, dg, db = native.group_norm_relu_bwd(d, rec["y"], rec["mean"], rec["rstd"], norm.weight.detach(),
+                                                        norm.bias.detach(), norm.num_groups, dgamma=gs if into else None,
+                                                        dbeta=bs if into else None, accumulate=into,
+                                                        out_dtype=dtype if native.is_pairs(dtype) else None)
+                grads[norm.weight], grads[norm.bias] = (None, None) if into else (dg, db)
+            else:
+                dy = native.act_bwd_(d, rec["y"], 1)
+                grads[conv.bias] = off.run(lambda dy=dy, conv=conv: native.bias_grad(dy, conv.out_channels), dy)
+            grads[conv.weight] = off.run(lambda rec=rec, dy=dy, conv=conv: native.conv_weight_grad(
+                rec["xw"], dy, conv.weight, operand=dtype), rec["xw"], dy)
+            wr = native.pack_conv_weight(conv.weight.detach(), dy.shape[-1], dt, rot180=True)
+            d = native.conv_fwd(dy, wr, None, conv.in_channels, 3)
+        B, H, W, C = st["feat_shape"]
+        dfeat = native.roi_align_bwd(d.view(-1, P * P, C), rois, (B, H, W, C), P, self.box_pooler.scale,
+                                     **self.box_pooler.options)
+        out = [grads[p] for p in bh.parameters()]
+        off.join(*out)
+        return dfeat.permute(0, 3, 1, 2), out
 
     # ---- label_and_sample_proposals (roi_heads.py:165-215) ----------------------------------------
     @torch.no_grad()

@@ -9,6 +9,7 @@ PyTorch is used here only as the owner of device memory and streams (``tensor.da
 """
 import collections
 import ctypes
+import math
 import os
 import re
 import warnings
@@ -198,6 +199,26 @@ def as_operand(t, dtype):
     operand pairs; half pairs -> bf16 pairs for a weight gradient whose producer did not write both).  The trunk's
     producers write operand tensors directly; the heads' small fp32 tensors pass here."""
     return t if t.dtype == dtype else cast(t, dtype)
+
+
+def conv3x3_channels(c, dt):
+    """the channel count the 3x3 convolution kernels take for a ``c``-channel input of storage type dt: whole chunks, a power
+    of two of them (gemm_conv.hip: ``Cin / chunk`` is a shift in the k loop)"""
+    e = chunk_elems(dt)
+    n = max((c + e - 1) // e, 1)
+    return e << (n - 1).bit_length()
+
+
+def pad_channels(x, cp):
+    """x [..., C] -> [..., cp] with zero channels behind (a copy; x itself when cp == C).  Pair tensors are moved as their
+    4-byte storage: 8-channel groups stay whole because C and cp are multiples of 8."""
+    c = x.shape[-1]
+    if cp == c:
+        return x
+    raw = torch.int32 if x.dtype in PAIR_DTYPES else x.dtype
+    out = torch.zeros(*x.shape[:-1], cp, dtype=raw, device=x.device)
+    out[..., :c] = x.view(raw)
+    return out.view(x.dtype)
 
 
 def operands_for(t, dtype, need_grad):
@@ -1025,6 +1046,41 @@ def bn_relu_pool_bwd(dz, y, mean, invstd, gamma, beta, pool, dgamma=None, dbeta=
     call("sfod_bn_relu_pool_bwd", dz, y, mean, invstd, gamma, beta, dy, dgamma, dbeta, dgamma_acc, dbeta_acc, ws,
          B, H, W, C,
          int(pool) | (0 if relu else 2), dt_of(y), dy_dt, nred)
+    return dy, dgamma, dbeta
+
+
+def group_norm_relu_fwd(y, gamma, beta, groups=32, eps=1e-5, relu=True, out_dtype=None, with_grad_operand=False):
+    """GroupNorm + ReLU of a convolution's output ``y`` [R, P, P, C] (or [R, PP, C]) -> (z, z_grad, mean, rstd).
+    ``out_dtype``: y.dtype, or a pair dtype from an fp32 y (the next layer's operand, written directly);
+    ``with_grad_operand``: ``z_grad`` is what that layer's weight gradient reads -- z itself, or for half pairs the same
+    values as bf16 pairs, written by the same pass (None without the flag).  mean / rstd: fp32 [R, groups], for the backward."""
+    R, C = y.shape[0], y.shape[-1]
+    PP = math.prod(y.shape[1:-1])
+    z = torch.empty(y.shape, dtype=out_dtype or y.dtype, device=y.device)
+    z2 = torch.empty(y.shape, dtype=SPLIT_DTYPE, device=y.device) if (with_grad_operand and z.dtype == SPLITH_DTYPE) else None
+    mean = torch.empty(R, groups, dtype=torch.float32, device=y.device)
+    rstd = torch.empty_like(mean)
+    call("sfod_group_norm_relu_fwd", y, gamma, beta, z, z2, mean, rstd, R, PP, C, groups, float(eps), int(relu), dt_of(y),
+         dt_of(z))
+    return z, ((z2 if z2 is not None else z) if with_grad_operand else None), mean, rstd
+
+
+def group_norm_relu_bwd(dz, y, mean, rstd, gamma, beta, groups=32, relu=True, dgamma=None, dbeta=None, accumulate=False,
+                        out_dtype=None):
+    """-> (dy, dgamma, dbeta).  ``out_dtype``: dtype of dy (y.dtype, or SPLIT_DTYPE from fp32 inputs: dy only feeds the wgrad /
+    dgrad MFMAs).  ``dgamma`` / ``dbeta`` given with ``accumulate``: gradient accumulators (see ``grad_sink``), added into."""
+    R, C = y.shape[0], y.shape[-1]
+    PP = math.prod(y.shape[1:-1])
+    assert dz.dtype == y.dtype and dz.shape == y.shape
+    assert not accumulate or (dgamma is not None and dbeta is not None)
+    dy = torch.empty(y.shape, dtype=out_dtype or y.dtype, device=y.device)
+    if dgamma is None:
+        dgamma = torch.empty(C, dtype=torch.float32, device=y.device)
+    if dbeta is None:
+        dbeta = torch.empty(C, dtype=torch.float32, device=y.device)
+    ws = torch.empty(query("sfod_group_norm_bwd_ws_floats", R, C), dtype=torch.float32, device=y.device)
+    call("sfod_group_norm_relu_bwd", dz, y, mean, rstd, gamma, beta, dy, dgamma, dbeta, ws, R, PP, C, groups, int(relu),
+         int(accumulate), dt_of(y), dt_of(dy))
     return dy, dgamma, dbeta
 
 
