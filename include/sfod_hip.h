@@ -623,6 +623,33 @@ int sfod_frcnn_loss_opt(const float* pred, int ld, int R, int K, const float* ro
                         float* loss, const float* grad_scale, float* d_pred, float* ws, float wx, float wy,
                         float ww, float wh, int loss_type, float beta, int cls_agnostic, void* stream);
 
+/* ---- Domain losses of DA Faster R-CNN (daod/modeling/meta_arch/da_faster_rcnn.py:228-272; csrc/da_losses.hip).  Logits
+ * are fp32 columns of a padded matrix: element i at z[i * ld] (the one-channel GEMM output under ldy = 8).  Gradients come
+ * back dense with the same ld, the padding columns zero.  grad_scale: device fp32 [1], the upstream d(total)/d(loss) (the
+ * sfod_rpn_loss convention).  No float atomics: every sum has one owner and a fixed order.
+ *
+ * sfod_da_bce: loss[0] = mean over the live rows of max(z, 0) - z * label + log1p(exp(-|z|)), loss[1] = the live count.
+ * rois ([n, 5], may be NULL): row i is padding (not live) when rois[5 i] < 0.  With grad_scale also
+ * dz[i * ld] = (sigmoid(z) - label) * g / n_live for live rows, 0 for the rest.  No live row: loss 0, gradient 0.
+ * ws: 2 * ceil(n / 256) floats. */
+int sfod_da_bce(const float* z, int64_t n, int ld, const float* rois, float label, float* loss,
+                const float* grad_scale, float* dz, float* ws, void* stream);
+/* sfod_da_consistency_fwd: z_img [B, H, W] with pixel stride ld, z_ins [R] with row stride ld_ins, rois [R, 5] (batch index
+ * < 0: padding).  Per live ROI p_img[r] = the mean over all pooled x pooled bins of ROIAlign (K13's definition, with its
+ * scale / sampling_ratio / aligned) applied to sigmoid(z_img); p_ins = sigmoid(z_ins[r]); loss[0] = mean over the live
+ * ROIs of |p_img - p_ins|, loss[1] = the live count.  Kept for the backward: sgn[r] = sign(p_img - p_ins) (0 at a tie and
+ * for padding), wts [R, H + W] = the ROI's separable pixel weights (Ay / (count pooled^2) | Ax); term [R] is scratch.
+ * No live ROI: loss 0 (torch's l1_loss of an empty tensor is NaN). */
+int sfod_da_consistency_fwd(const float* z_img, int B, int H, int W, int ld, const float* z_ins, int ld_ins,
+                            const float* rois, int R, int pooled, float scale, int sampling_ratio, int aligned,
+                            float* loss, float* p_img, float* sgn, float* term, float* wts, void* stream);
+/* dz_ins[r * ld_ins] = -sgn_r * g / n_live * p_ins (1 - p_ins); dz_img[b, y, x] = sigmoid'(z_img) * g / n_live *
+ * sum over the image's ROIs of sgn_r * Ay_r[y] * Ax_r[x] (one owner per pixel; 16 contiguous parts of the ROI rows, each summed in
+ * ROI order, added in part order).  loss / sgn / wts: the forward's. */
+int sfod_da_consistency_bwd(const float* z_img, int B, int H, int W, int ld, const float* z_ins, int ld_ins,
+                            const float* rois, int R, const float* loss, const float* sgn, const float* wts,
+                            const float* grad_scale, float* dz_img, float* dz_ins, void* stream);
+
 /* ---- K16: teacher inference post-processing (Appendix A.13; roi_heads.py:161) ----
  * step 1: softmax + per-class decode + clip + score filter -> candidates [B, P*K]
  *         (cand_scores = -1 for filtered entries), cand_count[b] = number passing. */

@@ -27,6 +27,7 @@ SOURCES = {
     "stem7x7.hip": [],
     "sort.hip": [],
     "augment.hip": ["-ffp-contract=off"],
+    "da_losses.hip": ["-ffp-contract=off"],
     "runtime.cpp": [],
 }
 HEADERS = ["common.h", "conv_internal.h", os.path.join("..", "..", "include", "sfod_hip.h")]

@@ -384,3 +384,56 @@ class FourWayLoader:
                 out = (self._label_bucket[:], self._label_key[:], self._unlabel_bucket[:], self._unlabel_key[:])
                 del self._label_bucket[:], self._label_key[:], self._unlabel_bucket[:], self._unlabel_key[:]
                 return out
+
+
+def semisup_batches(label_stream, unlabel_stream, batch_size_label, batch_size_unlabel):
+    """``AspectRatioGroupedSemiSupDataset.__iter__`` (daod/data/common.py:262-292) statement for statement over two streams
+    of dicts with "width" / "height": two aspect buckets (w > h | otherwise) per side; BOTH streams advance every iteration
+    and the element drawn for a side whose current bucket is already full is dropped; yields ``(label_batch,
+    unlabel_batch)`` once both current buckets are full."""
+    label_buckets, unlabel_buckets = [[], []], [[], []]
+    label_bucket, unlabel_bucket = [], []
+    for d_label, d_unlabel in zip(label_stream, unlabel_stream):
+        if len(label_bucket) != batch_size_label:
+            label_bucket = label_buckets[0 if d_label["width"] > d_label["height"] else 1]
+            label_bucket.append(d_label)
+        if len(unlabel_bucket) != batch_size_unlabel:
+            unlabel_bucket = unlabel_buckets[0 if d_unlabel["width"] > d_unlabel["height"] else 1]
+            unlabel_bucket.append(d_unlabel)
+        if len(label_bucket) == batch_size_label and len(unlabel_bucket) == batch_size_unlabel:
+            yield label_bucket[:], unlabel_bucket[:]
+            del label_bucket[:]
+            del unlabel_bucket[:]
+
+
+class DALoader:
+    """``build_detection_da_train_loader`` (daod/data/build.py:358-463) behind ``DATrainer.build_train_loader``: yields
+    ``(source_batch, target_batch)`` -- the weak frames of labelled ``DATASETS.TRAIN`` (``SOLVER.IMS_PER_BATCH // world`` per
+    rank) beside those of ``DATASETS.TRAIN_TARGET`` (``SOLVER.IMS_PER_BATCH_TARGET // world``; d2's ``DatasetMapper`` keeps
+    the target's annotations in the dicts, the model reads only the source's).  Batches form by ``semisup_batches``."""
+
+    def __init__(self, cfg, device, rank=0, world=1, source_dataset=None, target_dataset=None):
+        ns, nt = cfg.SOLVER.IMS_PER_BATCH, cfg.SOLVER.IMS_PER_BATCH_TARGET
+        # build.py:419-429 (the second message reports the SOURCE batch size: the reference's own slip, kept)
+        assert ns > 0 and ns % world == 0, \
+            "Total source batch size ({}) must be divisible by the number of gpus ({}).".format(ns, world)
+        assert nt > 0 and nt % world == 0, \
+            "Total target batch size ({}) must be divisible by the number of gpus ({}).".format(ns, world)
+        if "ASPECT_RATIO_GROUPING" in cfg.DATALOADER and not cfg.DATALOADER.ASPECT_RATIO_GROUPING:
+            raise NotImplementedError("ASPECT_RATIO_GROUPING = False is not supported yet")        # build.py:463
+        self.src = TwoCropLoader(cfg, device, rank, world, labeled=True, dataset=source_dataset)
+        self.tgt = TwoCropLoader(cfg, device, rank, world, labeled=False, dataset=target_dataset)
+        self.batch_size_source, self.batch_size_target = ns // world, nt // world
+        self._it = semisup_batches(self._stream(self.src), self._stream(self.tgt), self.batch_size_source,
+                                   self.batch_size_target)
+
+    @staticmethod
+    def _stream(side):
+        while True:
+            yield side._map(side.dataset.items[next(side.sampler)])
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._it)

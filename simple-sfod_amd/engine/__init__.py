@@ -1,5 +1,5 @@
 from .trainer import (BaseTrainer, SourceFreeAdaptiveTeacherTrainer,  # noqa: F401
-                      SourceFreeAdaptiveTeacherSingleTrainer, AdaptiveTeacherTrainer, adabn_refinement, test_refinement, get_trainer_class)
+                      SourceFreeAdaptiveTeacherSingleTrainer, AdaptiveTeacherTrainer, DATrainer, adabn_refinement, test_refinement, get_trainer_class)
 from .solver import (FusedSGD, FlatModelState, WarmupCosineLR, WarmupMultiStepLR, build_lr_scheduler,  # noqa: F401
                      build_optimizer)
 from . import planted  # noqa: F401

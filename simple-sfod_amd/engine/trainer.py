@@ -1174,8 +1174,33 @@ def test_refinement(cfg, model, data_loader, max_iters=1400, trainer_cls=None):
     return results
 
 
+class DATrainer(BaseTrainer):
+    """``TRAINER: "da"`` (daod/engine/trainers/da.py): DA Faster R-CNN.  The loader yields ``(source_batch, target_batch)``;
+    ``run_step`` is ``BaseTrainer``'s -- every ``loss*`` key of ``DAFasterRCNN`` summed, backward, the fused optimiser."""
+
+    def __init__(self, cfg, data_loader=None):
+        from ..modeling.da_options import validate_da_trainer_cfg
+        validate_da_trainer_cfg(cfg)
+        super().__init__(cfg, data_loader)
+
+    def _attach_reducer(self):
+        # the second domain passes the backbone too: no gradient slice is final when a backbone backward starts (the
+        # ``dc_live`` case of BaseTrainer._attach_reducer) -- one blocking exchange after the backward
+        self._reducer = None
+
+    @classmethod
+    def build_optimizer(cls, cfg, model):
+        # DC_img / DC_ins train in every step here, whatever the teacher-student trainers' DOMAIN_CLASSIFIER keys say
+        return build_optimizer(cfg, model, frozen=())
+
+    def build_train_loader(self, cfg):
+        from ..data.synthetic import DALoader
+        return DALoader(cfg, self.device, get_rank(), get_world_size())
+
+
 TRAINERS = {
     "base": BaseTrainer,
+    "da": DATrainer,
     "source_free_adaptive_teacher": SourceFreeAdaptiveTeacherTrainer,
     "source_free_adaptive_teacher_single": SourceFreeAdaptiveTeacherSingleTrainer,
     "adaptive_teacher": AdaptiveTeacherTrainer,
@@ -1186,4 +1211,7 @@ def get_trainer_class(cfg):
     """train_net_mt.py:48-69."""
     if cfg.TRAINER not in TRAINERS:
         raise ValueError(f"Trainer {cfg.TRAINER} not found.")
+    if cfg.TRAINER == "da":      # its loader feeds (source, target) tuples: only DAFasterRCNN takes them (a ValueError naming the key)
+        from ..modeling.da_options import validate_da_trainer_cfg
+        validate_da_trainer_cfg(cfg)
     return TRAINERS[cfg.TRAINER]

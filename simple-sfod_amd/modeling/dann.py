@@ -12,6 +12,9 @@ trains; the instance-level head has one too (``dc_ins_loss``: ROIAlign -> box he
 dropout -> BCE, ``source_free_adaptive_teacher_rcnn.py:157-201,341-349``), gradients reach the box head (any built head
 with NUM_FC >= 1: its parameter gradients come back as a list in ``box_head.parameters()`` order) and, through ROIAlign, the
 backbone.
+
+``DAImgHead`` ``:54-94`` is the image-level classifier of ``DAFasterRCNN`` (modeling/da_faster_rcnn.py), which also evaluates
+``DAInsHead`` through ``ins_head_logits`` / ``ins_head_backward`` below.
 """
 import torch
 import torch.nn as nn
@@ -240,3 +243,113 @@ def dc_ins_loss(roi_heads, head, feat_nchw, rois, domain_label, training=True):
     params = list(bh.parameters()) + [
               fc[0].weight, fc[0].bias, fc[1].weight, fc[1].bias, fc[2].weight, fc[2].bias]
     return _DCInsLossFn.apply(roi_heads, head, feat_nchw, rois, float(domain_label), masks, *params)
+
+
+class DAImgHead(nn.Module):
+    """Image-level domain classifier of DA Faster R-CNN (dann.py:54-94): per level ``Conv2d(C, 512, 1)`` + ReLU +
+    ``Conv2d(512, 1, 1)``, ``normal(std=0.001)`` / zero bias, modules ``DC_img_conv{1,2}_level_<level>``.  Both 1x1
+    convolutions run on the GEMM path over the map's pixels as rows; the one-channel output under ``ldy = 8``."""
+    HIDDEN = 512
+
+    def __init__(self, in_channels, levels, compute_dtype=torch.float32):
+        super().__init__()
+        self.da_img_conv1_layers, self.da_img_conv2_layers = [], []
+        for level in levels:
+            names = ["DC_img_conv{}_level_{}".format(k, level) for k in (1, 2)]
+            mods = [nn.Conv2d(in_channels, self.HIDDEN, kernel_size=1, stride=1), nn.Conv2d(self.HIDDEN, 1, kernel_size=1, stride=1)]
+            for m in mods:
+                nn.init.normal_(m.weight, std=0.001)
+                nn.init.constant_(m.bias, 0)
+            for n, m in zip(names, mods):
+                self.add_module(n, m)
+            self.da_img_conv1_layers.append(names[0])
+            self.da_img_conv2_layers.append(names[1])
+        self.compute_dtype = compute_dtype
+
+    def convs(self):
+        assert len(self.da_img_conv1_layers) == 1
+        return getattr(self, self.da_img_conv1_layers[0]), getattr(self, self.da_img_conv2_layers[0])
+
+    def logits(self, x_nhwc):
+        """x [B,H,W,C] operand -> (hidden activations [B*H*W, 512], fp32 logits [B,H,W,8], column 0 live)"""
+        dt = native.dt_of_dtype(self.compute_dtype)
+        c1, c2 = self.convs()
+        B, H, W, C = x_nhwc.shape
+        w1 = native.pack_fc_weight(c1.weight.detach().view(self.HIDDEN, C), dt)
+        h1 = native.conv_fwd(x_nhwc.view(B * H * W, C), w1, c1.bias.detach(), self.HIDDEN, 1, act=1)
+        w2 = native.pack_fc_weight(c2.weight.detach().view(1, self.HIDDEN), dt)
+        z = native.conv_fwd(h1, w2, c2.bias.detach(), 1, 1, out_dtype=torch.float32, ldy=8)
+        return h1, z.view(B, H, W, 8)
+
+    @torch.no_grad()
+    def forward(self, x):
+        """{level: [N,C,H,W]} (or the one level's tensor) -> the same with [N,1,H,W] fp32 logits.  Forward only: the
+        training step differentiates through ``da_domain_losses`` (modeling/da_faster_rcnn.py)."""
+        if isinstance(x, dict):
+            return {level: self.forward(x[level]) for level in x}
+        _, z = self.logits(native.nhwc_operand(x, self.compute_dtype))
+        return z[..., :1].permute(0, 3, 1, 2)
+
+    def grads(self, x_nhwc, h1, dz_params, dz_input):
+        """``dz_*`` fp32 [B,H,W,8] (column 0 live): the logit gradient the parameters take, and the one handed back to the
+        input (they differ by the gradient-scalar layers in front of the head) -> (dx [B,H,W,C], [dw1, db1, dw2, db2])"""
+        dtype = native.grad_dtype_of(self.compute_dtype)
+        dt = native.dt_of_dtype(dtype)
+        c1, c2 = self.convs()
+        B, H, W, C = x_nhwc.shape
+        M, HID = B * H * W, self.HIDDEN
+        w2t = native.pack_fc_weight(c2.weight.detach().view(1, HID), dt, transpose=True, ld=8)
+        dzp = native.cast(dz_params.view(M, 8), dtype)
+        dw2 = native.conv_wgrad(h1, dzp, 1, 1, operand=dtype).view(1, HID, 1, 1)
+        db2 = native.bias_grad(dz_params.view(M, 8), 1)
+        dh = native.act_bwd_(native.conv_fwd(dzp, w2t, None, HID, 1), h1, 1)
+        dw1 = native.conv_wgrad(x_nhwc.view(M, C), dh, HID, 1, operand=dtype).view(HID, C, 1, 1)
+        db1 = native.bias_grad(dh, HID)
+        dh = native.act_bwd_(native.conv_fwd(native.cast(dz_input.view(M, 8), dtype), w2t, None, HID, 1), h1, 1)
+        w1t = native.pack_fc_weight(c1.weight.detach().view(HID, C), dt, transpose=True)
+        dx = native.conv_fwd(dh, w1t, None, C, 1)
+        return dx.view(B, H, W, C), [dw1, db1, dw2, db2]
+
+
+def ins_head_layers(head):
+    assert len(head.da_ins_fc1_layers) == 1
+    return [getattr(head, n[0]) for n in (head.da_ins_fc1_layers, head.da_ins_fc2_layers, head.da_ins_fc3_layers)]
+
+
+def ins_head_logits(head, bf, masks, dtype):
+    """One evaluation of ``DAInsHead`` on box features ``bf`` [R, D]; ``masks``: its two dropout masks (uint8 [R,1024],
+    p = 0.5) or None (eval mode) -> state with the fp32 logits ``z`` [R, 8] (column 0 live)."""
+    dt = native.dt_of_dtype(dtype)
+    fc1, fc2, fc3 = ins_head_layers(head)
+    r1 = native.conv_fwd(bf, native.pack_fc_weight(fc1.weight.detach(), dt), fc1.bias.detach(), 1024, 1, act=1)
+    z1 = native.mul_mask_(r1.clone(), masks[0], 2.0) if masks is not None else r1
+    r2 = native.conv_fwd(z1, native.pack_fc_weight(fc2.weight.detach(), dt), fc2.bias.detach(), 1024, 1, act=1)
+    z2 = native.mul_mask_(r2.clone(), masks[1], 2.0) if masks is not None else r2
+    z = native.conv_fwd(z2, native.pack_fc_weight(fc3.weight.detach(), dt), fc3.bias.detach(), 1, 1,
+                        out_dtype=torch.float32, ldy=8)
+    return {"r1": r1, "z1": z1, "r2": r2, "z2": z2, "z": z, "masks": masks}
+
+
+def ins_head_backward(head, bf, ev, dz, compute_dtype):
+    """``dz`` fp32 [R, 8]: gradient of the logits of evaluation ``ev`` -> (d box features [R, D], [dw1, db1, .., db3])"""
+    dtype = native.grad_dtype_of(compute_dtype)
+    dt = native.dt_of_dtype(dtype)
+    fc1, fc2, fc3 = ins_head_layers(head)
+    masks = ev["masks"]
+    dzc = native.cast(dz, dtype)
+    dw3 = native.conv_wgrad(ev["z2"], dzc, 1, 1, operand=dtype).view(1, -1)
+    db3 = native.bias_grad(dz, 1)
+    d2 = native.conv_fwd(dzc, native.pack_fc_weight(fc3.weight.detach(), dt, transpose=True, ld=8), None, 1024, 1)
+    if masks is not None:
+        native.mul_mask_(d2, masks[1], 2.0)
+    native.act_bwd_(d2, ev["r2"], 1)
+    dw2 = native.conv_wgrad(ev["z1"], d2, 1024, 1, operand=dtype).view(1024, -1)
+    db2 = native.bias_grad(d2, 1024)
+    d1 = native.conv_fwd(d2, native.pack_fc_weight(fc2.weight.detach(), dt, transpose=True), None, 1024, 1)
+    if masks is not None:
+        native.mul_mask_(d1, masks[0], 2.0)
+    native.act_bwd_(d1, ev["r1"], 1)
+    dw1 = native.conv_wgrad(bf, d1, 1024, 1, operand=dtype).view(1024, -1)
+    db1 = native.bias_grad(d1, 1024)
+    dbf = native.conv_fwd(d1, native.pack_fc_weight(fc1.weight.detach(), dt, transpose=True), None, fc1.in_features, 1)
+    return dbf, [dw1, db1, dw2, db2, dw3, db3]

@@ -1,5 +1,5 @@
 """ROI heads on the HIP kernels behind ``StandardROIHeads`` /
-``SourceFreeAdaptiveTeacherStandardROIHeads`` / ``AdaptiveTeacherStandardROIHeads``.
+``SourceFreeAdaptiveTeacherStandardROIHeads`` / ``AdaptiveTeacherStandardROIHeads`` / ``DAStandardROIHeads``.
 
 Mirrors ``/root/reference/daod/modeling/roi_heads/source_free_adaptive_teacher_roi_heads.py``:
 ``_init_box_head`` ``:27-66``, ``forward`` ``:68-106`` (training+compute_loss -> label & sample,
@@ -671,3 +671,62 @@ class AdaptiveTeacherStandardROIHeads(StandardROIHeads):
         if cfg.MODEL.ROI_HEADS.LOSS == "CrossEntropy":
             return FastRCNNOutputLayers(cfg, shape)
         raise ValueError("Unknown ROI head loss.")
+
+
+@ROI_HEADS_REGISTRY.register()
+class DAStandardROIHeads(StandardROIHeads):
+    """``StandardROIHeads`` that returns the box features (da_roi_heads.py:15-129).  Training with targets: label and sample,
+    ``(samples, losses, box_features)``; training without: ``sample_unlabeled_proposals``, ``(samples, {}, box_features)``;
+    eval: ``(pred_instances, {})``.  ``samples`` is the fixed-capacity sample dict of ``label_and_sample_proposals``
+    (``rois`` [B * BATCH_SIZE_PER_IMAGE, 5], padding rows with batch index -1).
+
+    ``DAFasterRCNN`` (modeling/da_faster_rcnn.py) does not come through ``forward`` in training: it takes the samples from the
+    two sampling methods and runs ``_DADomainFn``, which makes the one box-head pass that serves the detection and the domain
+    losses.  ``forward`` is the module-level surface; its ``box_features`` are a detached copy from a pass of their own."""
+
+    @torch.no_grad()
+    def sample_unlabeled_proposals(self, proposals, keys=None):
+        """``randperm(len)[:BATCH_SIZE_PER_IMAGE]`` per image: the BATCH_SIZE_PER_IMAGE live proposals with the smallest
+        random key (all of them when fewer are live), every one labelled background.  ``keys`` int32 [B, P]: drawn like
+        ``label_and_sample_proposals`` draws them and forced the same way, by an attribute (``_forced_keys_unlabeled``: the
+        labelled side's ``_forced_keys`` has the width of proposals + ground truth)."""
+        boxes, count = proposals.boxes, proposals.count
+        B, P, _ = boxes.shape
+        dev = boxes.device
+        K = self.num_classes
+        live = torch.arange(P, device=dev)[None, :] < count[:, None]
+        cls = torch.where(live, K, -2).to(torch.int32).contiguous()      # -2: beyond the live prefix (sfod_subsample)
+        keys = keys if keys is not None else getattr(self, "_forced_keys_unlabeled", None)
+        if keys is None:
+            keys = torch.randint(0, 2 ** 31 - 1, (B, P), dtype=torch.int32, device=dev)
+        # positive fraction 0: there is no foreground to prefer
+        sidx, scnt = native.subsample_roi(cls, keys, self.batch_size_per_image, 0.0, K)
+        no_gt = torch.zeros(B, 1, 4, dtype=torch.float32, device=dev)
+        rois, gt_cls, gt_box, n_valid = native.roi_build_samples(boxes, cls, torch.zeros_like(cls), sidx, scnt, no_gt,
+                                                                 torch.zeros(B, dtype=torch.int32, device=dev))
+        return {"rois": rois, "gt_cls": gt_cls, "gt_box": gt_box, "n_valid": n_valid, "count": scnt, "sampled_idxs": sidx,
+                "image_sizes": proposals.image_sizes}
+
+    def forward(self, images, features, proposals, targets=None, as_instances=True, keys=None, want_box_features=True):
+        del images
+        feat = features[self.in_features[0]]
+        if not isinstance(proposals, BatchedProposals):
+            proposals = _proposals_from_instances(proposals, feat.device)
+        if not self.training:
+            pred_instances, _ = self._inference(feat, proposals)
+            return (pred_instances.to_instances() if as_instances else pred_instances), {}
+        if targets is not None:
+            if not isinstance(targets, BatchedGT):
+                targets = BatchedGT.from_instances(targets, feat.device)
+            samples = self.label_and_sample_proposals(proposals, targets, keys=keys)
+            l_cls, l_box = _ROILossFn.apply(self, feat, samples, *self._params())
+            self._last_pred = None
+            losses = {"loss_cls": l_cls, "loss_box_reg": l_box}
+        else:
+            samples = self.sample_unlabeled_proposals(proposals, keys=keys)
+            losses = {}
+        box_features = None
+        if want_box_features:
+            with torch.no_grad():
+                box_features = self.box_features(self._box_forward(feat, samples["rois"])).float()
+        return samples, losses, box_features

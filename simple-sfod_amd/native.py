@@ -1444,6 +1444,49 @@ def frcnn_loss(pred, K, rois, gt_cls, gt_box, n_valid, grad_scale=None, box_reg=
     return loss, d_pred
 
 
+def _logit_column(z):
+    """(tensor, rows, ld) of a one-channel fp32 logit matrix [..., ld] (the GEMM's output under ldy)"""
+    assert z.dtype == torch.float32 and z.is_contiguous()
+    ld = z.shape[-1]
+    return z, z.numel() // ld, ld
+
+
+def da_bce(z, label, rois=None, grad_scale=None):
+    """BCE-with-logits of column 0 of ``z`` [..., ld] against the constant ``label``, mean over the live rows (``rois``:
+    rows with batch index -1 are padding) -> (loss [2] = (value, live count), dz like ``z`` or None)."""
+    z, n, ld = _logit_column(z)
+    loss = torch.empty(2, dtype=torch.float32, device=z.device)
+    ws = torch.empty(max((n + 255) // 256, 1) * 2, dtype=torch.float32, device=z.device)
+    dz = torch.empty_like(z) if grad_scale is not None else None
+    call("sfod_da_bce", z, n, ld, rois, float(label), loss, grad_scale, dz, ws)
+    return loss, dz
+
+
+def da_consistency_fwd(z_img, z_ins, rois, pooled, scale, sampling_ratio=0, aligned=True):
+    """z_img [B, H, W, ld], z_ins [R, ld'] (column 0 each), rois [R, 5] -> (loss [2] = (value, live count), state for
+    ``da_consistency_bwd``).  ``state["p_img"]``: the per-ROI mean of ROIAlign(sigmoid(z_img))."""
+    B, H, W, ld = z_img.shape
+    R, ld_ins = z_ins.shape
+    assert z_img.dtype == torch.float32 and z_ins.dtype == torch.float32 and rois.shape == (R, 5)
+    dev = z_img.device
+    loss = torch.empty(2, dtype=torch.float32, device=dev)
+    per_roi = torch.empty(3, max(R, 1), dtype=torch.float32, device=dev)      # p_img | sgn | term
+    wts = torch.empty(max(R, 1), H + W, dtype=torch.float32, device=dev)
+    call("sfod_da_consistency_fwd", z_img, B, H, W, ld, z_ins, ld_ins, rois, R, int(pooled), float(scale),
+         int(sampling_ratio), int(aligned), loss, per_roi[0], per_roi[1], per_roi[2], wts)
+    return loss, {"loss": loss, "p_img": per_roi[0, :R], "sgn": per_roi[1], "wts": wts}
+
+
+def da_consistency_bwd(z_img, z_ins, rois, state, grad_scale):
+    """-> (dz_img like z_img, dz_ins like z_ins): dense, the padding columns zero"""
+    B, H, W, ld = z_img.shape
+    R, ld_ins = z_ins.shape
+    dz_img, dz_ins = torch.empty_like(z_img), torch.empty_like(z_ins)
+    call("sfod_da_consistency_bwd", z_img, B, H, W, ld, z_ins, ld_ins, rois, R, state["loss"], state["sgn"], state["wts"],
+         grad_scale, dz_img, dz_ins)
+    return dz_img, dz_ins
+
+
 def frcnn_inference(pred, K, props, prop_count, sizes, score_thresh, nms_thresh, max_det, pseudo_thr,
                     numel_limit=20000, box_reg=None):
     """Teacher post-processing -> dict of fixed-capacity per-image arrays + counts."""
