@@ -650,6 +650,36 @@ int sfod_da_consistency_bwd(const float* z_img, int B, int H, int W, int ld, con
                             const float* rois, int R, const float* loss, const float* sgn, const float* wts,
                             const float* grad_scale, float* dz_img, float* dz_ins, void* stream);
 
+/* ---- Class conditioning of conditional DA Faster R-CNN (daod/modeling/meta_arch/cda_faster_rcnn.py:22-33, 263-283;
+ * csrc/cda_condition.hip).  f [R, D]: the box features in storage type f_dt (any of the four), decoded to fp32.  scores: fp32,
+ * row r at scores + r * ld, C live columns (ld >= C).  rois [R, 5]: row r is padding when rois[5 r] < 0.  Per live row:
+ *   p = softmax(scores) (the maximum subtracted),
+ *   w = 1 + exp(sum_c p_c * log(p_c + 1e-5)) when entropy is 1 (the reference's entropy(): its fp32 1e-5 inside the log), else 1,
+ *   x[r, c * D + d] = p[r, c] * f[r, d]      (bmm(g.unsqueeze(2), f.unsqueeze(1)).view(R, -1)).
+ * The row's C scalars are formed in double (they cost nothing beside the C * D stores) and the product is rounded once to
+ * fp32 and from there to x's storage type, so x is that type's rounding of the exact product to double's precision; p and w
+ * come back as the fp32 roundings.
+ * x [R, C * D] is written in storage type x_dt, the operand of the product that follows; x_grad_operand (may be NULL; x_dt
+ * SFOD_F16X3 only): the same values once more as SFOD_BF16X3 pairs, the weight gradient's operand (the convention of
+ * sfod_group_norm_relu_fwd); a value beyond half's range is clamped and reported through sfod_f16x3_poll.  p [R, C] and
+ * w [R]: fp32, kept for the backward and the weighted loss.  A padding row gives zeros in x, p and w whatever its scores
+ * hold.  D a multiple of 8, 2 <= C <= 4096 (the row's probabilities sit in LDS); R == 0: no launch. */
+int sfod_cda_condition_fwd(const void* f, int f_dt, const float* scores, int ld, const float* rois, int R, int D, int C,
+                           int entropy, void* x, int x_dt, void* x_grad_operand, float* p, float* w, void* stream);
+/* df[r, d] = sum over c (ascending) of p[r, c] * dx[r, c * D + d], fused multiply-adds in double, rounded once to fp32 and
+ * from there to df's type; one owner per element; 0 for a
+ * padding row.  dx and df: dt SFOD_F32 or SFOD_BF16 (what the data-gradient product writes).  The condition is detached in
+ * the reference: there is no gradient to the scores. */
+int sfod_cda_condition_bwd(const void* dx, int dt, const float* p, const float* rois, int R, int D, int C, void* df,
+                           void* stream);
+/* sfod_da_bce with a weight per row (weight [n] fp32; rois may be NULL): loss[0] = sum_live w_i * bce_i / sum_live w_i (the
+ * reference's weight / weight.mean() followed by the mean), loss[1] = the live count, and with grad_scale
+ * dz[i * ld] = g * (w_i / sum_live w) * (sigmoid(z_i) - label) for live rows, 0 for the rest.  No live row, or live weights
+ * that sum to 0: loss 0, gradient 0.  ws: sfod_da_bce_weighted_ws_floats(n) floats.  n < 2^24. */
+int64_t sfod_da_bce_weighted_ws_floats(int64_t n);
+int sfod_da_bce_weighted(const float* z, int64_t n, int ld, const float* rois, const float* weight, float label, float* loss,
+                         const float* grad_scale, float* dz, float* ws, void* stream);
+
 /* ---- K16: teacher inference post-processing (Appendix A.13; roi_heads.py:161) ----
  * step 1: softmax + per-class decode + clip + score filter -> candidates [B, P*K]
  *         (cand_scores = -1 for filtered entries), cand_count[b] = number passing. */

@@ -28,6 +28,7 @@ SOURCES = {
     "sort.hip": [],
     "augment.hip": ["-ffp-contract=off"],
     "da_losses.hip": ["-ffp-contract=off"],
+    "cda_condition.hip": ["-ffp-contract=off"],
     "runtime.cpp": [],
 }
 HEADERS = ["common.h", "conv_internal.h", os.path.join("..", "..", "include", "sfod_hip.h")]

@@ -2542,5 +2542,6 @@ extern "C" int sfod_f16x3_poll(uint32_t* word, void* stream) {
   sfod_f16_poll_first(word, s);
   sfod_f16_poll_stem(word, s);
   sfod_f16_poll_gn(word, s);
+  sfod_f16_poll_cda(word, s);
   return sfod_check_launch("f16x3_poll");
 }

@@ -165,8 +165,13 @@ class DAFasterRCNN(GeneralizedRCNN):
             self.backbone.needed_features.add(self.da.level)
         self.DC_img = DAImgHead(self.backbone._out_feature_channels[self.da.level], self.levels,
                                 compute_dtype=self.compute_dtype)
-        self.DC_ins = DAInsHead(self.roi_heads.box_predictor.cls_score.in_features, self.levels,
-                                compute_dtype=self.compute_dtype)
+        self.DC_ins = DAInsHead(self._ins_head_in_features(), self.levels, compute_dtype=self.compute_dtype)
+
+    def _ins_head_in_features(self):
+        return self.roi_heads.box_predictor.cls_score.in_features
+
+    def _domain_losses(self, feat_nchw, samples, labeled, domain_label, masks):
+        return da_domain_losses(self, feat_nchw, samples, labeled, domain_label, masks)
 
     def _draw_masks(self, n_rois):
         """the dropout masks of one training step in the reference's call order, or what a test injected"""
@@ -190,7 +195,7 @@ class DAFasterRCNN(GeneralizedRCNN):
         proposals_s, proposal_losses = self.proposal_generator(images_s, features_s, gt, as_instances=False)
         losses = {}
         if batched_t is None:
-            _, detector_losses, _ = rh(images_s, features_s, proposals_s, gt, want_box_features=False)
+            _, detector_losses, *_ = rh(images_s, features_s, proposals_s, gt, want_box_features=False)
             losses.update(detector_losses)
             losses.update(proposal_losses)
             return losses
@@ -201,10 +206,10 @@ class DAFasterRCNN(GeneralizedRCNN):
             proposals_t, _ = self.proposal_generator(images_t, features_t, None, as_instances=False)
         samples_t = rh.sample_unlabeled_proposals(proposals_t)
         masks = self._draw_masks({"s": samples_s["rois"].shape[0], "t": samples_t["rois"].shape[0]})
-        l_cls, l_box, img_s, ins_s, cons_s = da_domain_losses(self, features_s[level], samples_s, True, 0,
-                                                              (masks["ins_s"], masks["cons_s"]))
-        _, _, img_t, ins_t, cons_t = da_domain_losses(self, features_t[level], samples_t, False, 1,
-                                                      (masks["ins_t"], masks["cons_t"]))
+        l_cls, l_box, img_s, ins_s, cons_s = self._domain_losses(features_s[level], samples_s, True, 0,
+                                                                 (masks["ins_s"], masks["cons_s"]))
+        _, _, img_t, ins_t, cons_t = self._domain_losses(features_t[level], samples_t, False, 1,
+                                                         (masks["ins_t"], masks["cons_t"]))
         losses.update({"loss_cls": l_cls, "loss_box_reg": l_box})
         losses.update(proposal_losses)
         losses["loss_DC_img"] = 0.5 * (img_s + img_t)

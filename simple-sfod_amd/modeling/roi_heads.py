@@ -1,5 +1,5 @@
 """ROI heads on the HIP kernels behind ``StandardROIHeads`` /
-``SourceFreeAdaptiveTeacherStandardROIHeads`` / ``AdaptiveTeacherStandardROIHeads`` / ``DAStandardROIHeads``.
+``SourceFreeAdaptiveTeacherStandardROIHeads`` / ``AdaptiveTeacherStandardROIHeads`` / ``DAStandardROIHeads`` / ``CDAStandardROIHeads``.
 
 Mirrors ``/root/reference/daod/modeling/roi_heads/source_free_adaptive_teacher_roi_heads.py``:
 ``_init_box_head`` ``:27-66``, ``forward`` ``:68-106`` (training+compute_loss -> label & sample,
@@ -730,3 +730,26 @@ class DAStandardROIHeads(StandardROIHeads):
             with torch.no_grad():
                 box_features = self.box_features(self._box_forward(feat, samples["rois"])).float()
         return samples, losses, box_features
+
+
+@ROI_HEADS_REGISTRY.register()
+class CDAStandardROIHeads(DAStandardROIHeads):
+    """``DAStandardROIHeads`` that also returns the class logits (cda_roi_heads.py:13-128): in training
+    ``(samples, losses, box_features, box_scores)``, the reference's return order; ``box_scores`` [R, K + 1] are the first
+    K + 1 columns of the fused prediction row, evaluated for the unlabeled (target) side too although it has no loss.
+
+    Like its parent, ``CDAFasterRCNN`` (modeling/cda_faster_rcnn.py) does not come through ``forward`` in training; the
+    features and logits returned here are detached copies from a pass of their own."""
+
+    def forward(self, images, features, proposals, targets=None, as_instances=True, keys=None, want_box_features=True):
+        out = super().forward(images, features, proposals, targets, as_instances=as_instances, keys=keys, want_box_features=False)
+        if not self.training:
+            return out
+        samples, losses, _ = out
+        box_features = box_scores = None
+        if want_box_features:
+            with torch.no_grad():
+                st = self._box_forward(features[self.in_features[0]], samples["rois"])
+                box_features = native.cast(self.box_features(st), torch.float32)
+                box_scores = st["pred"][:, : self.num_classes + 1].clone()
+        return samples, losses, box_features, box_scores

@@ -1487,6 +1487,44 @@ def da_consistency_bwd(z_img, z_ins, rois, state, grad_scale):
     return dz_img, dz_ins
 
 
+def cda_condition_fwd(f, scores, C, rois, entropy=False, out_dtype=None, with_grad_operand=False):
+    """Box features ``f`` [R, D] (any storage type), fp32 ``scores`` [R, ld] (the first ``C`` columns live), ``rois`` [R, 5] ->
+    (x [R, C * D] of ``out_dtype`` (default: f's), x_grad, p [R, C], w [R]): x[r, c * D + d] = softmax(scores)[r, c] * f[r, d],
+    written as the next GEMM's operand; ``x_grad``: what that GEMM's weight gradient reads -- x itself, or for half pairs the
+    same values as bf16 pairs from the same pass (None without ``with_grad_operand``); w = 1 + exp(-entropy(p)) with
+    ``entropy``, else 1.  Padding rows (batch index < 0) are zero everywhere."""
+    R, D = f.shape
+    assert scores.dtype == torch.float32 and scores.dim() == 2 and scores.shape[0] == R and rois.shape == (R, 5)
+    dev = f.device
+    x = torch.empty(R, C * D, dtype=out_dtype or f.dtype, device=dev)
+    x2 = torch.empty(R, C * D, dtype=SPLIT_DTYPE, device=dev) if (with_grad_operand and x.dtype == SPLITH_DTYPE) else None
+    p = torch.empty(R, C, dtype=torch.float32, device=dev)
+    w = torch.empty(R, dtype=torch.float32, device=dev)
+    call("sfod_cda_condition_fwd", f, dt_of(f), scores, scores.shape[1], rois, R, D, C, int(bool(entropy)), x, dt_of(x), x2, p, w)
+    return x, ((x2 if x2 is not None else x) if with_grad_operand else None), p, w
+
+
+def cda_condition_bwd(dx, p, rois):
+    """dx [R, C * D] (fp32 or bf16), p [R, C] -> df [R, D] = sum_c p[:, c] * dx[:, c * D:(c + 1) * D], padding rows 0"""
+    R, C = p.shape
+    D = dx.shape[1] // C
+    assert dx.shape == (R, C * D) and rois.shape == (R, 5)
+    df = torch.empty(R, D, dtype=dx.dtype, device=dx.device)
+    call("sfod_cda_condition_bwd", dx, dt_of(dx), p, rois, R, D, C, df)
+    return df
+
+
+def da_bce_weighted(z, label, weight, rois=None, grad_scale=None):
+    """``da_bce`` with a weight per row: the weighted mean ``sum w bce / sum w`` over the live rows and its gradient."""
+    z, n, ld = _logit_column(z)
+    assert weight.dtype == torch.float32 and weight.numel() == n
+    loss = torch.empty(2, dtype=torch.float32, device=z.device)
+    ws = torch.empty(query("sfod_da_bce_weighted_ws_floats", n), dtype=torch.float32, device=z.device)
+    dz = torch.empty_like(z) if grad_scale is not None else None
+    call("sfod_da_bce_weighted", z, n, ld, rois, weight, float(label), loss, grad_scale, dz, ws)
+    return loss, dz
+
+
 def frcnn_inference(pred, K, props, prop_count, sizes, score_thresh, nms_thresh, max_det, pseudo_thr,
                     numel_limit=20000, box_reg=None):
     """Teacher post-processing -> dict of fixed-capacity per-image arrays + counts."""
