@@ -622,6 +622,28 @@ int sfod_frcnn_loss_opt(const float* pred, int ld, int R, int K, const float* ro
                         const int32_t* gt_cls, const float* gt_box, const int32_t* n_valid,
                         float* loss, const float* grad_scale, float* d_pred, float* ws, float wx, float wy,
                         float ww, float wh, int loss_type, float beta, int cls_agnostic, void* stream);
+/* Most general form: the box options above plus the classification loss (MODEL.ROI_HEADS.LOSS,
+ * MODEL.ROI_BOX_HEAD.USE_SIGMOID_CE; definitions restated in tests/helpers/cls_loss_definitions.py).  Per live row r
+ * (gt_cls[r] = c >= 0), N = n_valid[0], g = grad_scale[0]:
+ *   cls_mode 0  cross-entropy: CE_r = logsumexp(z[0..K]) - z_c; loss[0] = sum CE / N.  What the two entry points above run.
+ *   cls_mode 1  focal (Unbiased Teacher's FastRCNNFocalLoss): p = exp(-CE), q = 1 - p taken as -expm1(-CE);
+ *               loss[0] = sum q^gamma CE / N; d/dz_j = A (softmax_j - [j == c]) g / N with
+ *               A = q^gamma (1 + gamma p CE / q), CE / q := 1 at q == 0.  gamma 0 is the cross-entropy (0^0 = 1).
+ *   cls_mode 2  sigmoid cross-entropy (d2 USE_SIGMOID_CE): target t = one-hot of c over K + 1 columns without the last, so a
+ *               background row has the all-zero target; loss[0] = sum_r sum_{j < K} (max(z_j, 0) - z_j t_j + log1p(exp(-|z_j|))) / N;
+ *               d/dz_j = (sigmoid(z_j) - t_j) g / N for j < K, the background column gets no gradient.
+ * Modes 1 and 2 form the row's scalars in double and round every gradient element once to fp32; the loss terms stay in
+ * double through the per-block partial and the final sum, so loss[0] is the fp32 rounding of its definition.  Both are
+ * finite for every gamma >= 0 at both ends of p; a NaN or +inf score gives a NaN loss, as in mode 0.  ws: 2 * ceil(R / 256)
+ * floats in mode 0 (as above), 3 * ceil(R / 256) in modes 1 and 2 (the class partial of a block is a pair of floats).
+ * gamma (read by mode 1 only) must be finite and >= 0 in every mode.  The box half (loss[1], the delta columns of d_pred)
+ * does not depend on cls_mode.  One owner per gradient element, no float atomics; padding rows and padding columns of
+ * d_pred are zero. */
+int sfod_frcnn_loss_cls(const float* pred, int ld, int R, int K, const float* rois,
+                        const int32_t* gt_cls, const float* gt_box, const int32_t* n_valid,
+                        float* loss, const float* grad_scale, float* d_pred, float* ws, float wx, float wy,
+                        float ww, float wh, int loss_type, float beta, int cls_agnostic, int cls_mode, float gamma,
+                        void* stream);
 
 /* ---- Domain losses of DA Faster R-CNN (daod/modeling/meta_arch/da_faster_rcnn.py:228-272; csrc/da_losses.hip).  Logits
  * are fp32 columns of a padded matrix: element i at z[i * ld] (the one-channel GEMM output under ldy = 8).  Gradients come
@@ -694,9 +716,22 @@ int sfod_frcnn_candidates_opt(const float* pred, int ld, int B, int P, int K, co
                               float score_thresh, float* cand_boxes, float* cand_scores,
                               int32_t* cand_count, float wx, float wy, float ww, float wh, int cls_agnostic,
                               void* stream);
+/* Most general form: cls_mode as in sfod_frcnn_loss_cls, here naming the row's class probabilities: 0 / 1 the row softmax
+ * (the operation order above), 2 the sigmoid 1 / (1 + exp(-z)) of each of the K + 1 scores (the finite test covers all K + 1;
+ * the last column is dropped as before).  One device function serves this kernel, sfod_predict_probs_cls and
+ * sfod_bpc_loss_cls.  The three take the class options as the loss does, cls_mode and gamma by value: gamma must be
+ * finite and >= 0 and no probability depends on it. */
+int sfod_frcnn_candidates_cls(const float* pred, int ld, int B, int P, int K, const float* props,
+                              const int32_t* prop_count, const int32_t* image_sizes,
+                              float score_thresh, float* cand_boxes, float* cand_scores,
+                              int32_t* cand_count, float wx, float wy, float ww, float wh, int cls_agnostic,
+                              int cls_mode, float gamma, void* stream);
 /* d2 FastRCNNOutputLayers.predict_probs (reached from daod/modeling/roi_heads/source_free_fast_rcnn.py:16-17): row
  * softmax of scores [R, ld] (K+1 class scores per row) -> probs [R, K+1], in step 1's operation order. */
 int sfod_predict_probs(const float* scores, int ld, int R, int K, float* probs, void* stream);
+/* General form: cls_mode 0 / 1 the row softmax, 2 the per-score sigmoid (sfod_frcnn_candidates_cls). */
+int sfod_predict_probs_cls(const float* scores, int ld, int R, int K, int cls_mode, float gamma, float* probs,
+                           void* stream);
 /* step 2 (after sorting scores): gather sorted candidates, classes, coordinate-offset boxes
  * and the torchvision strategy flag (mode[b]=1: coordinate trick, 0: per-class). */
 int sfod_frcnn_prepare_nms(const float* cand_boxes, const float* sorted_scores,
@@ -730,6 +765,11 @@ int sfod_bpc_loss_opt(const float* pred, int ld, int R, int K, const float* rois
                       int B, const int32_t* image_sizes, const float* gt_boxes, const int32_t* gt_classes,
                       const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws, float wx, float wy,
                       float ww, float wh, int cls_agnostic, void* stream);
+/* Most general form: cls_mode 0 / 1 scores by the row softmax, 2 by the per-score sigmoid (sfod_frcnn_candidates_cls). */
+int sfod_bpc_loss_cls(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,
+                      int B, const int32_t* image_sizes, const float* gt_boxes, const int32_t* gt_classes,
+                      const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws, float wx, float wy,
+                      float ww, float wh, int cls_agnostic, int cls_mode, float gamma, void* stream);
 
 /* F1Evaluator (daod/evaluation/f1_evaluator.py:8-230, appended to every trainer's evaluator list, base.py:149): per image
  * and class the counts TP / FP / FN that its F1 score is made of, one wavefront per image, nothing read back.

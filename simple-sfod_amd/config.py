@@ -226,6 +226,10 @@ def get_cfg():
     _C.MODEL.ROI_BOX_HEAD.CONV_DIM = 256      # their width: 8 x a power of two, <= 1024 (>= 32 under NORM "GN")
     _C.MODEL.ROI_BOX_HEAD.NORM = ""           # "" or "GN" = GroupNorm(32, CONV_DIM), eps 1e-5, conv bias off; BN / SyncBN / LN raise
     _C.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG = False
+    # Classification options (modeling/cls_loss_options.py, with MODEL.ROI_HEADS.LOSS and SFOD.FOCAL_LOSS_GAMMA).  Built:
+    # USE_SIGMOID_CE (d2: binary cross-entropy over the K foreground columns, probabilities by sigmoid).  USE_FED_LOSS True raises.
+    _C.MODEL.ROI_BOX_HEAD.USE_SIGMOID_CE = False
+    _C.MODEL.ROI_BOX_HEAD.USE_FED_LOSS = False
     _C.MODEL.ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES = False
     _C.MODEL.RESNETS = CN()
     _C.MODEL.RESNETS.DEPTH = 50
@@ -401,6 +405,7 @@ def add_native_config(cfg):
                           generic weight-gradient kernels are summed through slabs in a fixed order, so a step is
                           bit-identical from run to run (the reference on CUDA is not: cuDNN / atomicAdd); costs one
                           more pass over the split partials of the 1x1 / linear gradients (fc1: 2 x 103 MB).
+    SFOD.FOCAL_LOSS_GAMMA gamma of the ROI classifier's focal loss (MODEL.ROI_HEADS.LOSS "FocalLoss"), default 1.5.
     SFOD.EVALUATORS       what ``Trainer.build_evaluator`` builds, in order.  ("coco",) (default): the ``NewCOCOEvaluator``
                           alone -> ``{"bbox": {...}}``.  ("coco", "f1") is the reference's list (base.py:133-151): a
                           ``DatasetEvaluators`` of it and the ``F1Evaluator`` -> ``"bbox"`` and ``"F1 Score"``.  An
@@ -415,6 +420,9 @@ def add_native_config(cfg):
     _C.SFOD.ELIDE_DEAD_BRANCHES = True
     _C.SFOD.OVERLAP_TEACHER = True
     _C.SFOD.DETERMINISTIC = False
+    # gamma of MODEL.ROI_HEADS.LOSS "FocalLoss": (1 - p)^gamma * CE; finite and >= 0 (1.5: the constant of Unbiased Teacher's
+    # FastRCNNFocalLoss)
+    _C.SFOD.FOCAL_LOSS_GAMMA = 1.5
     # roctx ranges around the stages of a step (teacher / student_forward / student_backward / exchange / update) for
     # rocprofv3 --marker-trace; also SFOD_ROCTX=1 (engine/trainer.py::stage)
     _C.SFOD.PROFILE_RANGES = False

@@ -1265,33 +1265,158 @@ extern "C" int sfod_make_rois(const float* props, const int32_t* prop_count, int
 // ---------------------------------------------------------------------------------------------
 #define KMAX 32
 
+// Classification options of the Fast R-CNN head (include/sfod_hip.h: sfod_frcnn_loss_cls).
+#define CLS_CE 0          // softmax cross-entropy
+#define CLS_FOCAL 1       // (1 - p)^gamma * CE on the softmax cross-entropy
+#define CLS_SIGMOID 2     // binary cross-entropy with logits over the K foreground columns; probabilities by sigmoid
+
+// "The row's class probabilities", shared by k_frcnn_candidates, k_predict_probs and k_bpc_sums.  Softmax rows keep their
+// operation order (max, exp(x - max) summed in class order, one division per class); sigmoid rows need no row statistics.
+// A probability is cls_prob_of_num(cls_row_num(z)): the kernels that hold the row in a per-thread array keep the
+// numerators from the pass that sums them (KEEP), k_bpc_sums (registers only) forms them again -- the same operations on
+// the same values either way.
+struct RowNorm { float m, ssum; };
+
+__device__ __forceinline__ float cls_row_num(float z, RowNorm n, int cls_mode) {
+  return cls_mode != CLS_SIGMOID ? expf(z - n.m) : z;
+}
+
+__device__ __forceinline__ float cls_prob_of_num(float num, RowNorm n, int cls_mode) {
+  return cls_mode != CLS_SIGMOID ? num / n.ssum : 1.f / (1.f + expf(-num));
+}
+
+template <bool KEEP>
+__device__ __forceinline__ RowNorm cls_row_norm(const float* __restrict__ row, int K, int cls_mode, float* num) {
+  RowNorm n{0.f, 1.f};
+  if (cls_mode != CLS_SIGMOID) {
+    n.m = row[0];
+    for (int c = 1; c <= K; ++c) n.m = fmaxf(n.m, row[c]);
+    float ssum = 0.f;
+    for (int c = 0; c <= K; ++c) {
+      const float e = cls_row_num(row[c], n, cls_mode);
+      if (KEEP) num[c] = e;
+      ssum += e;
+    }
+    n.ssum = ssum;
+  } else if (KEEP) {
+    for (int c = 0; c <= K; ++c) num[c] = row[c];
+  }
+  return n;
+}
+
+__device__ __forceinline__ float cls_row_prob(float z, RowNorm n, int cls_mode) {
+  return cls_prob_of_num(cls_row_num(z, n, cls_mode), n, cls_mode);
+}
+
+static inline bool sfod_cls_mode_ok(int cls_mode) { return cls_mode == CLS_CE || cls_mode == CLS_FOCAL || cls_mode == CLS_SIGMOID; }
+
+// Focal and sigmoid rows of k_frcnn_loss: the row's scalars are formed in double (one row per thread: they cost nothing
+// beside the launch).  Every gradient element is rounded once to fp32; the row's loss term stays in double through the
+// block's partial and the final sum (k_frcnn_sum_wide), so loss[0] is the fp32 rounding of its definition -- also where the
+// fp32 textbook form is inf * 0 (focal, 0 < gamma < 1, a saturated row).  A NaN or +inf score gives a NaN term, as in mode 0.
+// Focal: CE = log(sum exp(z - m)) - (z_c - m), p = exp(-CE), q = 1 - p = -expm1(-CE); term q^gamma CE;
+//   d/dz_j = A (p_j - [j == c]) with A = q^gamma (1 + gamma p CE / q), CE / q := 1 at q == 0 (its limit).
+__device__ __forceinline__ double focal_row(const float* __restrict__ row, int K, int c, double gamma, double gs,
+                                           float* __restrict__ drow) {
+  double m = (double)row[0];
+  for (int j = 1; j <= K; ++j) m = fmax(m, (double)row[j]);
+  double ssum = 0.0;
+  for (int j = 0; j <= K; ++j) ssum += exp((double)row[j] - m);
+  double ce = log(ssum) - ((double)row[c] - m);
+  if (ce < 0.0) ce = 0.0;                             // rounding below 0 only: a NaN stays a NaN
+  const double p = exp(-ce), q = -expm1(-ce);
+  const double qg = pow(q, gamma);                    // pow(0, 0) == 1: gamma 0 is the cross-entropy
+  if (drow) {
+    const double A = qg * (1.0 + gamma * p * (q > 0.0 ? ce / q : 1.0));
+    for (int j = 0; j <= K; ++j) {
+      const double pj = exp((double)row[j] - m) / ssum;
+      drow[j] = (float)(A * (pj - (j == c ? 1.0 : 0.0)) * gs);
+    }
+  }
+  return qg * ce;
+}
+
+// Sigmoid: target = one-hot of c over K + 1 columns without the last; per column max(z, 0) - z t + log1p(exp(-|z|)) (the
+// form of sfod_da_bce), d/dz_j = sigmoid(z_j) - t_j; the background column takes no part and gets no gradient.
+__device__ __forceinline__ double sigmoid_ce_row(const float* __restrict__ row, int K, int c, double gs,
+                                                float* __restrict__ drow) {
+  double term = 0.0;
+  for (int j = 0; j < K; ++j) {
+    const double z = (double)row[j], t = (j == c) ? 1.0 : 0.0;
+    const double e = exp(-fabs(z));
+    term += fmax(z, 0.0) - z * t + log1p(e);
+    if (drow) drow[j] = (float)(((z >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e)) - t) * gs);
+  }
+  return term;
+}
+
+__device__ __forceinline__ double block_sum_d256(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+// The partial sums of k_frcnn_loss in modes 1 and 2: the class partial of block i is the double hi + lo with hi at
+// partial[2 i] and lo at partial[2 nblk + i]; summed in double, divided by N in double, rounded once.  The box half is
+// k_sum_partials2's, operation for operation.
+__global__ void __launch_bounds__(256)
+k_frcnn_sum_wide(const float* __restrict__ partial, int nblk, const int32_t* __restrict__ n_valid,
+                 float* __restrict__ loss) {
+  __shared__ float red[4];
+  __shared__ double redd[4];
+  double a = 0.0;
+  float c = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += 256) {
+    a += (double)partial[i * 2] + (double)partial[2 * nblk + i];
+    c += partial[i * 2 + 1];
+  }
+  a = block_sum_d256(a, redd);
+  c = block_sum_f256(c, red);
+  if (threadIdx.x == 0) {
+    const float nv = (float)n_valid[0];
+    loss[0] = nv > 0.f ? (float)(a / (double)n_valid[0]) : 0.f;
+    loss[1] = c / fmaxf(nv, 1.f);
+  }
+}
+
 __global__ void __launch_bounds__(256)
 k_frcnn_loss(const float* __restrict__ pred, int ld, int R, int K, const float* __restrict__ rois,
              const int32_t* __restrict__ gt_cls, const float* __restrict__ gt_box,
              const int32_t* __restrict__ n_valid, const float* __restrict__ grad_scale,
              float* __restrict__ d_pred, float* __restrict__ partial, BoxWeights bw, int loss_type, float beta,
-             int cls_agnostic) {
+             int cls_agnostic, int cls_mode, float gamma) {
   __shared__ float red[4];
+  __shared__ double redd[4];
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   float lcls = 0.f, lbox = 0.f;
+  double lcls_wide = 0.0;                             // modes 1 and 2
   if (r < R) {
     const int c = gt_cls[r];
     const float* row = pred + (int64_t)r * ld;
     float* drow = d_pred ? d_pred + (int64_t)r * ld : nullptr;
     if (c >= 0) {
-      float m = row[0];
-      for (int j = 1; j <= K; ++j) m = fmaxf(m, row[j]);
-      float ssum = 0.f;
-      for (int j = 0; j <= K; ++j) ssum += expf(row[j] - m);
-      const float lse = logf(ssum) + m;
-      lcls = lse - row[c];
       const float nv = (float)n_valid[0];
-      if (grad_scale) {
-        const float gs = grad_scale[0] / nv;
-        for (int j = 0; j <= K; ++j) {
-          const float pj = expf(row[j] - lse);
-          drow[j] = (pj - (j == c ? 1.f : 0.f)) * gs;
+      if (cls_mode == CLS_CE) {
+        float m = row[0];
+        for (int j = 1; j <= K; ++j) m = fmaxf(m, row[j]);
+        float ssum = 0.f;
+        for (int j = 0; j <= K; ++j) ssum += expf(row[j] - m);
+        const float lse = logf(ssum) + m;
+        lcls = lse - row[c];
+        if (grad_scale) {
+          const float gs = grad_scale[0] / nv;
+          for (int j = 0; j <= K; ++j) {
+            const float pj = expf(row[j] - lse);
+            drow[j] = (pj - (j == c ? 1.f : 0.f)) * gs;
+          }
         }
+      } else {
+        const double gs = grad_scale ? (double)grad_scale[0] / (double)n_valid[0] : 0.0;
+        lcls_wide = cls_mode == CLS_FOCAL ? focal_row(row, K, c, (double)gamma, gs, grad_scale ? drow : nullptr)
+                                          : sigmoid_ce_row(row, K, c, gs, grad_scale ? drow : nullptr);
       }
       if (c < K) {
         Box rb{rois[(int64_t)r * 5 + 1], rois[(int64_t)r * 5 + 2], rois[(int64_t)r * 5 + 3],
@@ -1307,16 +1432,27 @@ k_frcnn_loss(const float* __restrict__ pred, int ld, int R, int K, const float* 
       }
     }
   }
-  lcls = block_sum_f256(lcls, red);
-  lbox = block_sum_f256(lbox, red);
-  if (threadIdx.x == 0) { partial[blockIdx.x * 2] = lcls; partial[blockIdx.x * 2 + 1] = lbox; }
+  if (cls_mode == CLS_CE) {
+    lcls = block_sum_f256(lcls, red);
+    lbox = block_sum_f256(lbox, red);
+    if (threadIdx.x == 0) { partial[blockIdx.x * 2] = lcls; partial[blockIdx.x * 2 + 1] = lbox; }
+  } else {                                            // cls_mode is uniform: every thread of the block comes here
+    lcls_wide = block_sum_d256(lcls_wide, redd);
+    lbox = block_sum_f256(lbox, red);
+    if (threadIdx.x == 0) {
+      const float hi = (float)lcls_wide;
+      partial[blockIdx.x * 2] = hi;
+      partial[blockIdx.x * 2 + 1] = lbox;
+      partial[2 * gridDim.x + blockIdx.x] = (float)(lcls_wide - (double)hi);
+    }
+  }
 }
 
-extern "C" int sfod_frcnn_loss_opt(const float* pred, int ld, int R, int K, const float* rois,
+extern "C" int sfod_frcnn_loss_cls(const float* pred, int ld, int R, int K, const float* rois,
                                    const int32_t* gt_cls, const float* gt_box, const int32_t* n_valid,
                                    float* loss, const float* grad_scale, float* d_pred, float* ws, float wx,
                                    float wy, float ww, float wh, int loss_type, float beta, int cls_agnostic,
-                                   void* stream) {
+                                   int cls_mode, float gamma, void* stream) {
   SFOD_REQUIRE_EXTENTS("frcnn_loss", ld, R, K);
   // (no per-thread class array here, unlike the candidates kernel: K is bounded by the row only -- Detectron2's default 80
   // classes run through it in tests/test_gpu_d2_golden.py)
@@ -1324,6 +1460,11 @@ extern "C" int sfod_frcnn_loss_opt(const float* pred, int ld, int R, int K, cons
   SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "frcnn_loss: box weights must be finite and > 0");
   SFOD_REQUIRE(loss_type == BOXREG_SMOOTH_L1 || loss_type == BOXREG_GIOU, "frcnn_loss: loss_type must be 0 (smooth_l1) or 1 (giou)");
   SFOD_REQUIRE(beta >= 0.f && isfinite(beta), "frcnn_loss: beta must be finite and >= 0");
+  SFOD_REQUIRE(sfod_cls_mode_ok(cls_mode), "frcnn_loss: cls_mode must be 0 (cross-entropy), 1 (focal) or 2 (sigmoid cross-entropy)");
+  SFOD_REQUIRE(gamma >= 0.f && isfinite(gamma), "frcnn_loss: gamma must be finite and >= 0");
+  SFOD_REQUIRE(n_valid != nullptr && loss != nullptr && ws != nullptr, "frcnn_loss: null argument");
+  SFOD_REQUIRE(R == 0 || (pred != nullptr && rois != nullptr && gt_cls != nullptr && gt_box != nullptr),
+               "frcnn_loss: null argument");
   hipStream_t s = (hipStream_t)stream;
   if (grad_scale) {
     SFOD_REQUIRE(d_pred != nullptr, "d_pred");
@@ -1331,11 +1472,24 @@ extern "C" int sfod_frcnn_loss_opt(const float* pred, int ld, int R, int K, cons
   }
   const int nblk = cdiv(R, 256);
   hipLaunchKernelGGL(k_frcnn_loss, dim3(nblk), dim3(256), 0, s, pred, ld, R, K, rois, gt_cls, gt_box,
-                     n_valid, grad_scale, d_pred, ws, BoxWeights{wx, wy, ww, wh}, loss_type, beta, cls_agnostic != 0);
+                     n_valid, grad_scale, d_pred, ws, BoxWeights{wx, wy, ww, wh}, loss_type, beta, cls_agnostic != 0,
+                     cls_mode, gamma);
   int rc = sfod_check_launch("frcnn_loss");
   if (rc) return rc;
-  hipLaunchKernelGGL(k_sum_partials2, dim3(1), dim3(256), 0, s, ws, nblk, 1.f, 1.f, n_valid, loss);
+  if (cls_mode == CLS_CE)
+    hipLaunchKernelGGL(k_sum_partials2, dim3(1), dim3(256), 0, s, ws, nblk, 1.f, 1.f, n_valid, loss);
+  else
+    hipLaunchKernelGGL(k_frcnn_sum_wide, dim3(1), dim3(256), 0, s, ws, nblk, n_valid, loss);
   return sfod_check_launch("frcnn_loss_sum");
+}
+
+extern "C" int sfod_frcnn_loss_opt(const float* pred, int ld, int R, int K, const float* rois,
+                                   const int32_t* gt_cls, const float* gt_box, const int32_t* n_valid,
+                                   float* loss, const float* grad_scale, float* d_pred, float* ws, float wx,
+                                   float wy, float ww, float wh, int loss_type, float beta, int cls_agnostic,
+                                   void* stream) {
+  return sfod_frcnn_loss_cls(pred, ld, R, K, rois, gt_cls, gt_box, n_valid, loss, grad_scale, d_pred, ws, wx, wy, ww, wh,
+                             loss_type, beta, cls_agnostic, CLS_CE, 0.f, stream);
 }
 
 extern "C" int sfod_frcnn_loss(const float* pred, int ld, int R, int K, const float* rois,
@@ -1353,7 +1507,7 @@ __global__ void __launch_bounds__(256)
 k_frcnn_candidates(const float* __restrict__ pred, int ld, int P, int K, const float* __restrict__ props,
                    const int32_t* __restrict__ pc, const int32_t* __restrict__ sizes, float thr,
                    float* __restrict__ cboxes, float* __restrict__ cscores, int32_t* ccount, BoxWeights bw,
-                   int cls_agnostic) {
+                   int cls_agnostic, int cls_mode) {
   const int b = blockIdx.y;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   int npass = 0;
@@ -1365,11 +1519,8 @@ k_frcnn_candidates(const float* __restrict__ pred, int ld, int P, int K, const f
     Box bx[KMAX];
     bool fin = true;
     if (live) {
-      float m = row[0];
-      for (int c = 1; c <= K; ++c) m = fmaxf(m, row[c]);
-      float ssum = 0.f;
-      for (int c = 0; c <= K; ++c) { prob[c] = expf(row[c] - m); ssum += prob[c]; }
-      for (int c = 0; c <= K; ++c) { prob[c] = prob[c] / ssum; fin = fin && isfinite(prob[c]); }
+      const RowNorm rn = cls_row_norm<true>(row, K, cls_mode, prob);
+      for (int c = 0; c <= K; ++c) { prob[c] = cls_prob_of_num(prob[c], rn, cls_mode); fin = fin && isfinite(prob[c]); }
       Box pb = load_box(props + r * 4);
       for (int c = 0; c < K; ++c) {
         const float* d = row + K + 1 + (cls_agnostic ? 0 : c * 4);     // class-agnostic: every class decodes to the same box
@@ -1391,21 +1542,35 @@ k_frcnn_candidates(const float* __restrict__ pred, int ld, int P, int K, const f
   if ((threadIdx.x & 63) == 0 && npass) atomicAdd(ccount + b, npass);
 }
 
-extern "C" int sfod_frcnn_candidates_opt(const float* pred, int ld, int B, int P, int K, const float* props,
+extern "C" int sfod_frcnn_candidates_cls(const float* pred, int ld, int B, int P, int K, const float* props,
                                          const int32_t* prop_count, const int32_t* image_sizes,
                                          float score_thresh, float* cand_boxes, float* cand_scores,
                                          int32_t* cand_count, float wx, float wy, float ww, float wh,
-                                         int cls_agnostic, void* stream) {
+                                         int cls_agnostic, int cls_mode, float gamma, void* stream) {
   SFOD_REQUIRE_EXTENTS("frcnn_candidates", ld, B, P, K);
+  SFOD_REQUIRE(gamma >= 0.f && isfinite(gamma), "frcnn_candidates: gamma must be finite and >= 0");
   SFOD_REQUIRE(K <= KMAX && ld >= (cls_agnostic ? K + 5 : 5 * K + 1), "frcnn_candidates K / ld");
   SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "frcnn_candidates: box weights must be finite and > 0");
+  SFOD_REQUIRE(sfod_cls_mode_ok(cls_mode), "frcnn_candidates: cls_mode must be 0, 1 (softmax probabilities) or 2 (sigmoid)");
+  SFOD_REQUIRE(B == 0 || cand_count != nullptr, "frcnn_candidates: null argument");
+  SFOD_REQUIRE(B == 0 || P == 0 || (pred != nullptr && props != nullptr && prop_count != nullptr && image_sizes != nullptr &&
+                                    cand_boxes != nullptr && cand_scores != nullptr), "frcnn_candidates: null argument");
   hipStream_t s = (hipStream_t)stream;
   (void)hipMemsetAsync(cand_count, 0, sizeof(int32_t) * B, s);
   dim3 grid(cdiv(P, 256), B);
   hipLaunchKernelGGL(k_frcnn_candidates, grid, dim3(256), 0, s, pred, ld, P, K, props, prop_count,
                      image_sizes, score_thresh, cand_boxes, cand_scores, cand_count, BoxWeights{wx, wy, ww, wh},
-                     cls_agnostic != 0);
+                     cls_agnostic != 0, cls_mode);
   return sfod_check_launch("frcnn_candidates");
+}
+
+extern "C" int sfod_frcnn_candidates_opt(const float* pred, int ld, int B, int P, int K, const float* props,
+                                         const int32_t* prop_count, const int32_t* image_sizes,
+                                         float score_thresh, float* cand_boxes, float* cand_scores,
+                                         int32_t* cand_count, float wx, float wy, float ww, float wh,
+                                         int cls_agnostic, void* stream) {
+  return sfod_frcnn_candidates_cls(pred, ld, B, P, K, props, prop_count, image_sizes, score_thresh, cand_boxes,
+                                   cand_scores, cand_count, wx, wy, ww, wh, cls_agnostic, CLS_CE, 0.f, stream);
 }
 
 extern "C" int sfod_frcnn_candidates(const float* pred, int ld, int B, int P, int K, const float* props,
@@ -1421,25 +1586,30 @@ extern "C" int sfod_frcnn_candidates(const float* pred, int ld, int B, int P, in
 // order, one division per class) -- the probabilities the Instances-level API returns ARE the ones the fused teacher
 // post-processing thresholds.
 __global__ void __launch_bounds__(256)
-k_predict_probs(const float* __restrict__ scores, int ld, int R, int K, float* __restrict__ probs) {
+k_predict_probs(const float* __restrict__ scores, int ld, int R, int K, float* __restrict__ probs, int cls_mode) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
   const float* row = scores + r * ld;
   float prob[KMAX + 1];
-  float m = row[0];
-  for (int c = 1; c <= K; ++c) m = fmaxf(m, row[c]);
-  float ssum = 0.f;
-  for (int c = 0; c <= K; ++c) { prob[c] = expf(row[c] - m); ssum += prob[c]; }
-  for (int c = 0; c <= K; ++c) probs[r * (K + 1) + c] = prob[c] / ssum;
+  const RowNorm rn = cls_row_norm<true>(row, K, cls_mode, prob);
+  for (int c = 0; c <= K; ++c) probs[r * (K + 1) + c] = cls_prob_of_num(prob[c], rn, cls_mode);
+}
+
+extern "C" int sfod_predict_probs_cls(const float* scores, int ld, int R, int K, int cls_mode, float gamma, float* probs,
+                                      void* stream) {
+  SFOD_REQUIRE_EXTENTS("predict_probs", ld, R, K);
+  SFOD_REQUIRE(gamma >= 0.f && isfinite(gamma), "predict_probs: gamma must be finite and >= 0");
+  SFOD_REQUIRE(K >= 1 && K <= KMAX && ld >= K + 1, "predict_probs K / ld");
+  SFOD_REQUIRE(sfod_cls_mode_ok(cls_mode), "predict_probs: cls_mode must be 0, 1 (softmax probabilities) or 2 (sigmoid)");
+  if (R == 0) return 0;
+  SFOD_REQUIRE(scores != nullptr && probs != nullptr, "predict_probs: null argument");
+  hipLaunchKernelGGL(k_predict_probs, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, scores, ld, R, K, probs,
+                     cls_mode);
+  return sfod_check_launch("predict_probs");
 }
 
 extern "C" int sfod_predict_probs(const float* scores, int ld, int R, int K, float* probs, void* stream) {
-  SFOD_REQUIRE_EXTENTS("predict_probs", ld, R, K);
-  SFOD_REQUIRE(K >= 1 && K <= KMAX && ld >= K + 1, "predict_probs K / ld");
-  if (R == 0) return 0;
-  SFOD_REQUIRE(scores != nullptr && probs != nullptr, "predict_probs: null argument");
-  hipLaunchKernelGGL(k_predict_probs, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, scores, ld, R, K, probs);
-  return sfod_check_launch("predict_probs");
+  return sfod_predict_probs_cls(scores, ld, R, K, CLS_CE, 0.f, probs, stream);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1555,8 +1725,8 @@ k_bpc_sums(const float* __restrict__ pred, int ld, int R, int K, const float* __
            const int32_t* __restrict__ roi_cls, const int32_t* __restrict__ sizes,
            const float* __restrict__ gboxes, const int32_t* __restrict__ gcls,
            const int32_t* __restrict__ gcount, int B, int G, float iou_thr, double* __restrict__ sums,
-           BoxWeights bw, int cls_agnostic) {
-  // one thread per (sampled row, class); the row's softmax and finite test are recomputed by its K threads
+           BoxWeights bw, int cls_agnostic, int cls_mode) {
+  // one thread per (sampled row, class); the row's probabilities and finite test are recomputed by its K threads
   // (registers only: no per-thread class arrays)
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int r = (int)(t / K), c = (int)(t - (int64_t)r * K);
@@ -1569,13 +1739,10 @@ k_bpc_sums(const float* __restrict__ pred, int ld, int R, int K, const float* __
   if (b >= 0) {
     const float* roi = rois + (int64_t)r * 5;
     const float* row = pred + (int64_t)r * ld;
-    float m = row[0];
-    for (int k = 1; k <= K; ++k) m = fmaxf(m, row[k]);
-    float ssum = 0.f;
-    for (int k = 0; k <= K; ++k) ssum += expf(row[k] - m);
+    const RowNorm rn = cls_row_norm<false>(row, K, cls_mode, nullptr);
     bool fin = true;
-    for (int k = 0; k <= K; ++k) fin = fin && isfinite(expf(row[k] - m) / ssum);
-    const float sc = expf(row[c] - m) / ssum;
+    for (int k = 0; k <= K; ++k) fin = fin && isfinite(cls_row_prob(row[k], rn, cls_mode));
+    const float sc = cls_row_prob(row[c], rn, cls_mode);
     const int gtc = min(max(roi_cls[r], 0), K - 1);
     const float* dg = row + K + 1 + (cls_agnostic ? 0 : gtc * 4);
     const Box pb = apply_deltas(Box{roi[1], roi[2], roi[3], roi[4]}, dg[0], dg[1], dg[2], dg[3], bw.x, bw.y, bw.w, bw.h);
@@ -1643,24 +1810,39 @@ __global__ void k_bpc_final(const double* __restrict__ sums, int B, float* __res
   out[0] = n ? tot / (float)n : 0.f;
 }
 
-extern "C" int sfod_bpc_loss_opt(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,
+extern "C" int sfod_bpc_loss_cls(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,
                                  int B, const int32_t* image_sizes, const float* gt_boxes, const int32_t* gt_classes,
                                  const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws, float wx,
-                                 float wy, float ww, float wh, int cls_agnostic, void* stream) {
+                                 float wy, float ww, float wh, int cls_agnostic, int cls_mode, float gamma,
+                                 void* stream) {
   SFOD_REQUIRE_EXTENTS("bpc_loss", ld, R, K, B, G);
+  SFOD_REQUIRE(gamma >= 0.f && isfinite(gamma), "bpc_loss: gamma must be finite and >= 0");
   SFOD_REQUIRE(K >= 1 && K <= KMAX && ld >= (cls_agnostic ? K + 5 : 5 * K + 1), "bpc_loss K / ld");
   SFOD_REQUIRE(sfod_box_weights_ok(wx, wy, ww, wh), "bpc_loss: box weights must be finite and > 0");
+  SFOD_REQUIRE(sfod_cls_mode_ok(cls_mode), "bpc_loss: cls_mode must be 0, 1 (softmax probabilities) or 2 (sigmoid)");
+  SFOD_REQUIRE(loss != nullptr && ws != nullptr, "bpc_loss: null argument");
+  SFOD_REQUIRE(!(B > 0 && R > 0) || (pred != nullptr && rois != nullptr && roi_cls != nullptr && image_sizes != nullptr &&
+                                     gt_boxes != nullptr && gt_classes != nullptr && gt_count != nullptr),
+               "bpc_loss: null argument");
   hipStream_t s = (hipStream_t)stream;
   if (B > 0) (void)hipMemsetAsync(ws, 0, sizeof(double) * 4 * B, s);
   if (B > 0 && R > 0) {
     hipLaunchKernelGGL(k_bpc_sums, dim3(cdiv((int64_t)R * K, 256)), dim3(256), 0, s, pred, ld, R, K, rois, roi_cls,
                        image_sizes, gt_boxes, gt_classes, gt_count, B, G, iou_thresh, (double*)ws,
-                       BoxWeights{wx, wy, ww, wh}, cls_agnostic != 0);
+                       BoxWeights{wx, wy, ww, wh}, cls_agnostic != 0, cls_mode);
   }
   int rc = sfod_check_launch("bpc_sums");
   if (rc) return rc;
   hipLaunchKernelGGL(k_bpc_final, dim3(1), dim3(64), 0, s, (const double*)ws, B, loss);
   return sfod_check_launch("bpc_final");
+}
+
+extern "C" int sfod_bpc_loss_opt(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,
+                                 int B, const int32_t* image_sizes, const float* gt_boxes, const int32_t* gt_classes,
+                                 const int32_t* gt_count, int G, float iou_thresh, float* loss, void* ws, float wx,
+                                 float wy, float ww, float wh, int cls_agnostic, void* stream) {
+  return sfod_bpc_loss_cls(pred, ld, R, K, rois, roi_cls, B, image_sizes, gt_boxes, gt_classes, gt_count, G, iou_thresh,
+                           loss, ws, wx, wy, ww, wh, cls_agnostic, CLS_CE, 0.f, stream);
 }
 
 extern "C" int sfod_bpc_loss(const float* pred, int ld, int R, int K, const float* rois, const int32_t* roi_cls,

@@ -31,7 +31,7 @@ from .batched import gather_gt
 from .da_options import da_options
 from .dann import DAImgHead, DAInsHead, ins_head_backward, ins_head_layers, ins_head_logits
 from .meta_arch import GeneralizedRCNN
-from .roi_heads import DAStandardROIHeads  # noqa: F401  (the ROI heads of this architecture live beside the others)
+from .roi_heads import DAStandardROIHeads, _cls_kw  # noqa: F401  (the ROI heads of this architecture live beside the others)
 from .rpn import RPN
 
 MASK_ORDER = ("ins_s", "ins_t", "cons_s", "cons_t")      # the reference's call order of DAInsHead in one training step
@@ -85,7 +85,7 @@ class _DADomainFn(torch.autograd.Function):
         if labeled:
             bp = heads.box_predictor
             loss, _ = native.frcnn_loss(st["pred"], heads.num_classes, rois, samples["gt_cls"], samples["gt_box"],
-                                        samples["n_valid"], box_reg=bp._box_reg)
+                                        samples["n_valid"], box_reg=bp._box_reg, **_cls_kw(bp))
             ctx.box_w = bp.box_reg_loss_weight
             l_cls, l_box = loss[0].clone(), (loss[1].clone() if ctx.box_w == 1.0 else loss[1] * ctx.box_w)
         # image level: one evaluation of DAImgHead for the BCE term and the consistency term
@@ -131,7 +131,8 @@ class _DADomainFn(torch.autograd.Function):
                 g_box = g_box * ctx.box_w
             gs = torch.stack([g_cls.reshape(()), g_box.reshape(())]).float().contiguous()
             _, d_pred = native.frcnn_loss(st["pred"], heads.num_classes, rois, samples["gt_cls"], samples["gt_box"],
-                                          samples["n_valid"], grad_scale=gs, box_reg=heads.box_predictor._box_reg)
+                                          samples["n_valid"], grad_scale=gs, box_reg=heads.box_predictor._box_reg,
+                                          **_cls_kw(heads.box_predictor))
             dh, pred_grads = _predictor_backward(heads, st, d_pred)
             dbf = dbf + dh
         dfeat_roi, head_grads = heads._box_head_backward(st, rois, dbf.contiguous())

@@ -25,6 +25,7 @@ from .offchain import OffChain as _OffChain, heads_on as _heads_on
 from .batched import BatchedDetections, BatchedGT, BatchedProposals
 from .box_head_options import GN_EPS, GN_GROUPS, box_head_options
 from .box_regression import ROI_DEFAULT_WEIGHTS, roi_box_reg_options
+from .cls_loss_options import native_cls_loss
 from .proposal_options import roi_iou_band
 from .roi_pooler import roi_pooler_options
 
@@ -91,7 +92,7 @@ class FastRCNNConvFCHead(nn.Module):
 
 
 class FastRCNNOutputLayers(nn.Module):
-    def __init__(self, cfg, input_shape):
+    def __init__(self, cfg, input_shape, roi_heads_name=None):
         super().__init__()
         d = input_shape.channels * (input_shape.height or 1) * (input_shape.width or 1)      # d2: a (C, H, W) input is flattened
         self.num_classes = cfg.MODEL.ROI_HEADS.NUM_CLASSES
@@ -101,6 +102,10 @@ class FastRCNNOutputLayers(nn.Module):
         self.box_reg_loss_type, self.smooth_l1_beta = self.box_reg.loss_type, self.box_reg.beta
         self.box_reg_weights, self.cls_agnostic_bbox_reg = self.box_reg.weights, self.box_reg.cls_agnostic
         self._box_reg = None if self.box_reg.is_default(ROI_DEFAULT_WEIGHTS) else self.box_reg
+        # MODEL.ROI_HEADS.LOSS / SFOD.FOCAL_LOSS_GAMMA / MODEL.ROI_BOX_HEAD.USE_SIGMOID_CE (modeling/cls_loss_options.py; a
+        # ValueError naming the key for what is not built), under the ROI heads that build this predictor; ``_cls_loss`` is
+        # what the native calls take: None = the entry points of before these keys were read
+        self._cls_loss = native_cls_loss(cfg, roi_heads_name)
         self.cls_score = nn.Linear(d, self.num_classes + 1)
         self.bbox_pred = nn.Linear(d, 4 if self.cls_agnostic_bbox_reg else self.num_classes * 4)
         nn.init.normal_(self.cls_score.weight, std=0.01)
@@ -144,8 +149,11 @@ class _PredictorAPI:
 
     def predict_probs(self, predictions, proposals):
         scores, _ = predictions
-        # the library's row softmax (sfod_predict_probs: the fused teacher post-processing's own operation order)
-        return native.predict_probs(scores.float()).split([len(p) for p in proposals], dim=0)
+        # the library's row softmax (sfod_predict_probs: the fused teacher post-processing's own operation order), or under
+        # USE_SIGMOID_CE its sigmoid of every score
+        cl = self._cls_loss
+        probs = native.predict_probs(scores.float(), **({"cls_loss": cl} if cl is not None else {}))
+        return probs.split([len(p) for p in proposals], dim=0)
 
     def predict_boxes_for_gt_classes(self, predictions, proposals):
         if not len(proposals):
@@ -206,6 +214,12 @@ class SourceFreeFastRCNNOutputLayers(FastRCNNOutputLayers):
         return res, inds[:, 0]
 
 
+def _cls_kw(box_predictor):
+    """the ``cls_loss`` keyword of a native call: absent with every classification key at its default (the call of before)"""
+    cl = box_predictor._cls_loss
+    return {} if cl is None else {"cls_loss": cl}
+
+
 class InstanceProposals:
     """4th value of the training-mode ROI heads (``instance_proposals``,
     source_free_adaptive_teacher_roi_heads.py:101,158): the per-class decoded predictions of the sampled
@@ -220,7 +234,8 @@ class InstanceProposals:
         sizes = native.dev_const(tuple((int(s[0]), int(s[1])) for s in sm["image_sizes"]), torch.int32,
                                  self.pred.device)
         return native.bpc_loss(self.pred, h.num_classes, sm["rois"], sm["gt_cls"], sizes, targets.boxes,
-                               targets.classes, targets.count, iou_thresh, box_reg=h.box_predictor._box_reg)
+                               targets.classes, targets.count, iou_thresh, box_reg=h.box_predictor._box_reg,
+                               **_cls_kw(h.box_predictor))
 
     def to_instances(self):
         h, sm = self.heads, self.samples
@@ -249,7 +264,7 @@ class _ROILossFn(torch.autograd.Function):
         st = heads._box_forward(feat_nchw, samples["rois"])
         bp = heads.box_predictor
         loss, _ = native.frcnn_loss(st["pred"], heads.num_classes, samples["rois"], samples["gt_cls"],
-                                    samples["gt_box"], samples["n_valid"], box_reg=bp._box_reg)
+                                    samples["gt_box"], samples["n_valid"], box_reg=bp._box_reg, **_cls_kw(bp))
         ctx.heads, ctx.st, ctx.samples = heads, st, samples
         ctx.feat_shape = feat_nchw.shape
         heads._last_pred = st["pred"]          # for InstanceProposals (BPC); alive until the backward anyway
@@ -266,7 +281,7 @@ class _ROILossFn(torch.autograd.Function):
         gs = torch.stack([g_cls.reshape(()), g_box.reshape(())]).float().contiguous()
         _, d_pred = native.frcnn_loss(st["pred"], heads.num_classes, samples["rois"], samples["gt_cls"],
                                       samples["gt_box"], samples["n_valid"], grad_scale=gs,
-                                      box_reg=heads.box_predictor._box_reg)
+                                      box_reg=heads.box_predictor._box_reg, **_cls_kw(heads.box_predictor))
         dfeat, pgrads = heads._box_backward(st, samples["rois"], d_pred, ctx.feat_shape)
         ctx.st = None
         return (None, dfeat, None) + tuple(pgrads)
@@ -308,7 +323,7 @@ class StandardROIHeads(nn.Module):
         self.train_on_pred_boxes = cfg.MODEL.ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES
 
     def _make_predictor(self, cfg, shape):
-        return FastRCNNOutputLayers(cfg, shape)
+        return FastRCNNOutputLayers(cfg, shape, roi_heads_name=type(self).__name__)
 
     def _params(self):
         bh, bp = self.box_head, self.box_predictor
@@ -604,7 +619,7 @@ class StandardROIHeads(nn.Module):
                                          feat.device)
         out = native.frcnn_inference(st["pred"], self.num_classes, proposals.boxes, proposals.count, sizes_dev,
                                      bp.test_score_thresh, bp.test_nms_thresh, bp.test_topk_per_image,
-                                     self.bbox_threshold, self.nms_numel_limit, box_reg=bp._box_reg)
+                                     self.bbox_threshold, self.nms_numel_limit, box_reg=bp._box_reg, **_cls_kw(bp))
         return BatchedDetections(out, proposals.image_sizes), st["pred"]
 
     # ---- module surface (roi_heads.py:68-106) -------------------------------------------------------
@@ -660,17 +675,15 @@ def _proposals_from_instances(instances, device):
 @ROI_HEADS_REGISTRY.register()
 class SourceFreeAdaptiveTeacherStandardROIHeads(StandardROIHeads):
     def _make_predictor(self, cfg, shape):
-        if cfg.MODEL.ROI_HEADS.LOSS == "CrossEntropy":
-            return SourceFreeFastRCNNOutputLayers(cfg, shape)
-        raise ValueError("Unknown ROI head loss.")
+        # "CrossEntropy" / "FocalLoss" (FastRCNNFocaltLossOutputLayers of the code this descends from: the same layers, another
+        # loss_cls -- here ``box_predictor._cls_loss``); anything else: a ValueError naming the key
+        return SourceFreeFastRCNNOutputLayers(cfg, shape, roi_heads_name="SourceFreeAdaptiveTeacherStandardROIHeads")
 
 
 @ROI_HEADS_REGISTRY.register()
 class AdaptiveTeacherStandardROIHeads(StandardROIHeads):
     def _make_predictor(self, cfg, shape):
-        if cfg.MODEL.ROI_HEADS.LOSS == "CrossEntropy":
-            return FastRCNNOutputLayers(cfg, shape)
-        raise ValueError("Unknown ROI head loss.")
+        return FastRCNNOutputLayers(cfg, shape, roi_heads_name="AdaptiveTeacherStandardROIHeads")
 
 
 @ROI_HEADS_REGISTRY.register()

@@ -1220,6 +1220,41 @@ class BoxRegOptions:
         return f"BoxRegOptions({self.weights}, {self.loss_type!r}, beta={self.beta}, cls_agnostic={self.cls_agnostic})"
 
 
+CLS_LOSS_KINDS = {"CrossEntropy": 0, "FocalLoss": 1}      # cls_mode of the ``*_cls`` entry points; 2 = sigmoid cross-entropy
+
+
+class ClsLossOptions:
+    """Classification options of the Fast R-CNN head, as the ``sfod_*_cls`` entry points take them: ``kind``
+    ("CrossEntropy" / "FocalLoss": MODEL.ROI_HEADS.LOSS), the focal ``gamma`` (SFOD.FOCAL_LOSS_GAMMA) and ``sigmoid``
+    (MODEL.ROI_BOX_HEAD.USE_SIGMOID_CE: binary cross-entropy over the K foreground columns, probabilities by sigmoid).  The
+    wrappers below take ``cls_loss=None`` for today's entry points and an instance for the ``*_cls`` forms (which, given the
+    default values, compute the same bits)."""
+    __slots__ = ("kind", "gamma", "sigmoid")
+
+    def __init__(self, kind="CrossEntropy", gamma=1.5, sigmoid=False):
+        self.kind, self.gamma, self.sigmoid = str(kind), float(gamma), bool(sigmoid)
+        if self.kind not in CLS_LOSS_KINDS:
+            raise ValueError(f"ClsLossOptions: kind must be one of {sorted(CLS_LOSS_KINDS)}, got {kind!r}")
+        if self.sigmoid and self.kind != "CrossEntropy":
+            raise ValueError(f"ClsLossOptions: sigmoid excludes kind {self.kind!r} (the focal loss is defined on the softmax)")
+
+    @property
+    def mode(self):
+        return 2 if self.sigmoid else CLS_LOSS_KINDS[self.kind]
+
+    def is_default(self):
+        return self.kind == "CrossEntropy" and not self.sigmoid
+
+    def __repr__(self):
+        return f"ClsLossOptions({self.kind!r}, gamma={self.gamma}, sigmoid={self.sigmoid})"
+
+
+def _box_reg_args(box_reg):
+    """(wx, wy, ww, wh, cls_agnostic) of a ROI head's ``box_reg`` (None: Detectron2's defaults, what the plain entry points run)"""
+    return (*(box_reg.weights if box_reg is not None else (10.0, 10.0, 5.0, 5.0)),
+            int(box_reg.cls_agnostic) if box_reg is not None else 0)
+
+
 _RPN_UNIT_WEIGHTS = (1.0, 1.0, 1.0, 1.0)
 
 
@@ -1430,13 +1465,19 @@ def roi_align_bwd(dout, rois, feat_shape, pooled, scale, dfeat=None, sampling_ra
     return dfeat
 
 
-def frcnn_loss(pred, K, rois, gt_cls, gt_box, n_valid, grad_scale=None, box_reg=None):
+def frcnn_loss(pred, K, rois, gt_cls, gt_box, n_valid, grad_scale=None, box_reg=None, cls_loss=None):
     R, ld = pred.shape
     dev = pred.device
     loss = torch.empty(2, dtype=torch.float32, device=dev)
-    ws = torch.empty(((R + 255) // 256) * 2, dtype=torch.float32, device=dev)
+    # per block two partials; the ``_cls`` form's modes 1 and 2 keep the class partial as a pair of floats: three
+    ws = torch.empty(((R + 255) // 256) * (2 if cls_loss is None else 3), dtype=torch.float32, device=dev)
     d_pred = torch.empty_like(pred) if grad_scale is not None else None
-    if box_reg is None:
+    if cls_loss is not None:
+        w = _box_reg_args(box_reg)
+        call("sfod_frcnn_loss_cls", pred, ld, R, K, rois, gt_cls, gt_box, n_valid, loss, grad_scale, d_pred, ws, *w[:4],
+             BOX_REG_LOSS_TYPES[box_reg.loss_type] if box_reg is not None else 0, box_reg.beta if box_reg is not None else 0.0,
+             w[4], cls_loss.mode, cls_loss.gamma)
+    elif box_reg is None:
         call("sfod_frcnn_loss", pred, ld, R, K, rois, gt_cls, gt_box, n_valid, loss, grad_scale, d_pred, ws)
     else:
         call("sfod_frcnn_loss_opt", pred, ld, R, K, rois, gt_cls, gt_box, n_valid, loss, grad_scale, d_pred, ws,
@@ -1526,7 +1567,7 @@ def da_bce_weighted(z, label, weight, rois=None, grad_scale=None):
 
 
 def frcnn_inference(pred, K, props, prop_count, sizes, score_thresh, nms_thresh, max_det, pseudo_thr,
-                    numel_limit=20000, box_reg=None):
+                    numel_limit=20000, box_reg=None, cls_loss=None):
     """Teacher post-processing -> dict of fixed-capacity per-image arrays + counts."""
     B, P, _ = props.shape
     dev = pred.device
@@ -1534,7 +1575,10 @@ def frcnn_inference(pred, K, props, prop_count, sizes, score_thresh, nms_thresh,
     cb = torch.empty(B, n, 4, dtype=torch.float32, device=dev)
     cs = torch.empty(B, n, dtype=torch.float32, device=dev)
     cc = torch.empty(B, dtype=torch.int32, device=dev)
-    if box_reg is None:
+    if cls_loss is not None:
+        call("sfod_frcnn_candidates_cls", pred, pred.shape[-1], B, P, K, props, prop_count, sizes, float(score_thresh),
+             cb, cs, cc, *_box_reg_args(box_reg), cls_loss.mode, cls_loss.gamma)
+    elif box_reg is None:
         call("sfod_frcnn_candidates", pred, pred.shape[-1], B, P, K, props, prop_count, sizes, float(score_thresh),
              cb, cs, cc)
     else:
@@ -1564,12 +1608,17 @@ def frcnn_inference(pred, K, props, prop_count, sizes, score_thresh, nms_thresh,
     return out
 
 
-def bpc_loss(pred, K, rois, roi_cls, sizes_dev, gt_boxes, gt_classes, gt_count, iou_thresh=0.5, box_reg=None):
+def bpc_loss(pred, K, rois, roi_cls, sizes_dev, gt_boxes, gt_classes, gt_count, iou_thresh=0.5, box_reg=None,
+             cls_loss=None):
     """BPC calibration scalar of one training pass (fused convert_bbox_scores + bpc_loss) -> 0-dim tensor."""
     B, G = gt_classes.shape
     loss = torch.empty(1, dtype=torch.float32, device=pred.device)
     ws = torch.empty(max(B, 1) * 4, dtype=torch.float64, device=pred.device)
-    if box_reg is None:
+    if cls_loss is not None:
+        call("sfod_bpc_loss_cls", pred, pred.shape[-1], pred.shape[0], K, rois, roi_cls, B, sizes_dev, gt_boxes,
+             gt_classes, gt_count, G, float(iou_thresh), loss, ws, *_box_reg_args(box_reg), cls_loss.mode,
+             cls_loss.gamma)
+    elif box_reg is None:
         call("sfod_bpc_loss", pred, pred.shape[-1], pred.shape[0], K, rois, roi_cls, B, sizes_dev, gt_boxes, gt_classes,
              gt_count, G, float(iou_thresh), loss, ws)
     else:
@@ -1596,14 +1645,19 @@ def f1_count(det_boxes, det_scores, det_classes, det_count, gt_boxes, gt_classes
     return counts
 
 
-def predict_probs(scores):
-    """Row softmax of the class scores [R, K+1] (any row stride) in the teacher post-processing kernel's operation order."""
+def predict_probs(scores, cls_loss=None):
+    """Row softmax of the class scores [R, K+1] (any row stride) in the teacher post-processing kernel's operation order;
+    under ``cls_loss.sigmoid`` the sigmoid of every score."""
     assert scores.is_cuda, "native ops need device tensors"
     assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.stride(1) == 1
     R, n = scores.shape
     out = torch.empty(R, n, dtype=torch.float32, device=scores.device)
     # (rows may be a strided view of the prediction matrix: the pointer goes in as is, the row stride as ld)
-    call("sfod_predict_probs", scores.data_ptr(), scores.stride(0) if R > 1 else n, R, n - 1, out)
+    if cls_loss is not None:
+        call("sfod_predict_probs_cls", scores.data_ptr(), scores.stride(0) if R > 1 else n, R, n - 1, cls_loss.mode,
+             cls_loss.gamma, out)
+    else:
+        call("sfod_predict_probs", scores.data_ptr(), scores.stride(0) if R > 1 else n, R, n - 1, out)
     return out
 
 
