@@ -84,6 +84,24 @@ int sfod_resize_bilinear_u8_opt(const void* src, void* dst, int C, int H, int W,
                                 const int32_t* vbounds, const int32_t* vcoef, int ksize_v, int flip_mode,
                                 void* stream);
 
+/* Mosaic composition of one training image in one launch (daod/data/mappers/mosaic.py:81-265, MosaicDetection.__getitem__):
+ *   canvas [2*H0][2*W0] = fill;  for tile k in order:  canvas[ly1:ly2, lx1:lx2] = U_k[sy1:sy2, sx1:sx2]  with
+ *   U_k = PIL.resize(tile_k [3,h0,w0], (w, h), BILINEAR), bit for bit (the arithmetic of sfod_resize_bilinear_u8);
+ *   out [3,H0,W0][c][y][x] = (canvas[2y][2x] + canvas[2y][2x+1] + canvas[2y+1][2x] + canvas[2y+1][2x+1] + 2) >> 2.
+ * Neither the canvas nor any U_k is written to memory.  tiles, tabs and geom are HOST arrays, read before the call returns
+ * (the geometry travels in the launch arguments, nothing is uploaded):
+ *   tiles [n_tiles]      device pointers to the uint8 [3,h0,w0] tiles
+ *   tabs  [n_tiles][2]   device pointers to the horizontal (w0 -> w) and vertical (h0 -> h) table of each tile: int32 bounds
+ *                        [out][2] = (first source index, tap count) immediately followed by int32 coefficients [out][ksize]
+ *                        (the layout sfod_resize_bilinear_u8 takes as two pointers).  Both NULL: identity scale, the tile is
+ *                        already at canvas scale (h == h0, w == w0) and is copied.
+ *   geom  [n_tiles][14]  int32: h0, w0, h, w, lx1, ly1, lx2, ly2, sx1, sy1, sx2, sy2, ksize_h, ksize_v
+ * Refused with SFOD_EBADARG before any launch (out untouched): n_tiles outside 1..4, fill outside 0..255, a NULL tile / out,
+ * one table of a tile NULL, a paste rectangle that leaves the canvas, a source rectangle that leaves its up-scaled tile,
+ * rectangles whose two sides differ in extent, a table-less tile that is not at canvas scale. */
+int sfod_mosaic_u8(const void* const* tiles, const void* const* tabs, const int32_t* geom, int n_tiles, int fill,
+                   void* out, int H0, int W0, void* stream);
+
 /* ---- K2/K5/K14/K18: implicit-GEMM convolution / linear layer on MFMA.
  * y[m, n] = act( sum_{tap, c} x[pix(m) + tap][c] * w[n][tap][c] + bias[n] ),  m = (b, oy, ox)
  * x: [B,H,W,Cin] NHWC, w: packed [Cout][KH*KW][Cin] (K contiguous), y: [B,H,W,ldy] with ldy >=

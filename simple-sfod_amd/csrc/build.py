@@ -27,6 +27,7 @@ SOURCES = {
     "stem7x7.hip": [],
     "sort.hip": [],
     "augment.hip": ["-ffp-contract=off"],
+    "mosaic.hip": [],
     "da_losses.hip": ["-ffp-contract=off"],
     "cda_condition.hip": ["-ffp-contract=off"],
     "runtime.cpp": [],

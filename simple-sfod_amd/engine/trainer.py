@@ -419,7 +419,8 @@ class BaseTrainer:
         if get_world_size() > 1 and not dc_live:
             # the mid phase: the backbone says which slice of its gradients is final while its backward still runs and calls
             # ``_mid_backward`` there (VGG: the deep stages once vgg<s> is done; ResNet-C4: res4 once its first block is done)
-            total = cfg.SOLVER.IMS_PER_BATCH if type(self) is BaseTrainer else cfg.SOLVER.IMS_PER_BATCH_TARGET
+            # (base and the source trainers that differ from it only in their loader read SOLVER.IMS_PER_BATCH)
+            total = cfg.SOLVER.IMS_PER_BATCH if type(self) in SOURCE_TRAINERS else cfg.SOLVER.IMS_PER_BATCH_TARGET
             b_local = max(1, int(total) // get_world_size())
             # (multi-scale training: the smallest short edge; 0 = "no resize" says nothing about the size)
             sizes = [int(v) for v in cfg.INPUT.MIN_SIZE_TRAIN if int(v) > 0]
@@ -1198,8 +1199,42 @@ class DATrainer(BaseTrainer):
         return DALoader(cfg, self.device, get_rank(), get_world_size())
 
 
+class BaseMosaicTrainer(BaseTrainer):
+    """``TRAINER: "base_mosaic"`` (daod/engine/trainers/base_mosaic.py): ``base`` on mosaics of four mapped source frames
+    (data/mosaic.py); only the loader differs."""
+    MOSAIC_VARIANT = "mosaic"
+
+    def build_train_loader(self, cfg):
+        from ..data.mosaic import MosaicLoader
+        return MosaicLoader(cfg, self.device, get_rank(), get_world_size(), variant=self.MOSAIC_VARIANT)
+
+
+class BaseMosaicWQTrainer(BaseMosaicTrainer):
+    """``TRAINER: "base_mosaic_wq"`` (base_mosaic_wq.py): the strong augmentation once, on the finished mosaic."""
+    MOSAIC_VARIANT = "mosaic_wq"
+
+
+class BaseMosaicWQNewTrainer(BaseMosaicTrainer):
+    """``TRAINER: "base_mosaic_wq_new"`` (base_mosaic_wq_new.py): the strong augmentation on every tile, before the paste."""
+    MOSAIC_VARIANT = "mosaic_wq_new"
+
+
+class BaseWQTrainer(BaseTrainer):
+    """``TRAINER: "base_wq"`` (base_wq.py): ``base`` with the strong augmentation on every mapped frame."""
+
+    def build_train_loader(self, cfg):
+        from ..data.mosaic import StrongLoader
+        return StrongLoader(cfg, self.device, get_rank(), get_world_size())
+
+
+SOURCE_TRAINERS = (BaseTrainer, BaseMosaicTrainer, BaseMosaicWQTrainer, BaseMosaicWQNewTrainer, BaseWQTrainer)
+
 TRAINERS = {
     "base": BaseTrainer,
+    "base_mosaic": BaseMosaicTrainer,
+    "base_mosaic_wq": BaseMosaicWQTrainer,
+    "base_mosaic_wq_new": BaseMosaicWQNewTrainer,
+    "base_wq": BaseWQTrainer,
     "da": DATrainer,
     "source_free_adaptive_teacher": SourceFreeAdaptiveTeacherTrainer,
     "source_free_adaptive_teacher_single": SourceFreeAdaptiveTeacherSingleTrainer,

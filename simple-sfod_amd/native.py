@@ -545,6 +545,49 @@ def weak_augment_u8(img, window, out_hw, flip_mode, out=None):
     return out
 
 
+def _axis_tab_base(device, in_size, out_size):
+    """-> (pointer to one axis' table as sfod_mosaic_u8 takes it: bounds [out][2] immediately followed by coefficients
+    [out][ksize], ksize).  That is how ``_axis_tabs`` uploads an axis (one tensor, two views)."""
+    b, k, ksize = _axis_tabs(device, in_size, out_size)
+    assert k.data_ptr() == b.data_ptr() + 4 * b.numel(), "the coefficient table must follow its bounds"
+    return b.data_ptr(), ksize
+
+
+def mosaic_u8(tiles, up_hw, rects, out_hw, fill=114, out=None):
+    """The mosaic of up to four uint8 [3,h0,w0] device tiles in ONE launch (sfod_mosaic_u8): tile k is scaled to ``up_hw[k]``
+    = (h, w) like ``PIL.resize(..., BILINEAR)`` bit for bit, its window ``rects[k][1]`` = (sx1, sy1, sx2, sy2) is pasted at
+    ``rects[k][0]`` = (lx1, ly1, lx2, ly2) of a [2*H0, 2*W0] canvas filled with ``fill`` (in order: later tiles overwrite
+    earlier ones), and the canvas is halved with the rounded 2x2 mean -> uint8 [3,H0,W0] with (H0, W0) = ``out_hw``.  Neither
+    the canvas nor an up-scaled tile is materialised.  A tile whose (h, w) equals its own size is copied (no tables).  Bad
+    rectangles are refused by the library (NativeLibraryError) and ``out`` stays untouched."""
+    n = len(tiles)
+    assert n == len(up_hw) == len(rects)
+    H0, W0 = int(out_hw[0]), int(out_hw[1])
+    dev = tiles[0].device
+    ptrs = (ctypes.c_void_p * max(n, 1))()
+    tabs = (ctypes.c_void_p * max(2 * n, 1))()
+    geom = (ctypes.c_int32 * max(14 * n, 1))()
+    tiles = [t.contiguous() for t in tiles]
+    for k, t in enumerate(tiles):
+        assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[0] == 3 and t.is_cuda
+        h0, w0 = int(t.shape[1]), int(t.shape[2])
+        h, w = int(up_hw[k][0]), int(up_hw[k][1])
+        ksh = ksv = 1
+        if (h, w) != (h0, w0) and min(h, w, h0, w0) >= 1:
+            tabs[2 * k], ksh = _axis_tab_base(dev, w0, w)
+            tabs[2 * k + 1], ksv = _axis_tab_base(dev, h0, h)
+        ptrs[k] = t.data_ptr()
+        geom[14 * k:14 * k + 14] = [h0, w0, h, w] + [int(v) for v in rects[k][0]] + [int(v) for v in rects[k][1]] + [ksh, ksv]
+    if out is None:
+        out = torch.empty(3, max(H0, 0), max(W0, 0), dtype=torch.uint8, device=dev)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (3, H0, W0)
+    lib = load()
+    rc = lib.sfod_mosaic_u8(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(tabs, ctypes.c_void_p),
+                            ctypes.cast(geom, ctypes.c_void_p), n, int(fill), out.data_ptr(), H0, W0, _stream())
+    _chk(rc, "sfod_mosaic_u8")
+    return out
+
+
 AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE, AUG_GRAYSCALE = 0, 1, 2, 3, 4
 _aug_ws = {}
 
