@@ -293,7 +293,8 @@ int sfod_unpack_conv_wgrad(const float* dw_packed, float* dw_oihw, int Cout, int
                            int CinPad, int accumulate, void* stream);
 /* nn.Linear weight [N][K] fp32 -> [N][Kperm] (dt) where, if chw_c > 0, the K axis is permuted
  * from (c, p) (flatten of [C,7,7], d2 FastRCNNConvFCHead) to (p, c) (our ROIAlign layout);
- * transpose=1 writes [K][N] instead (the dgrad operand). */
+ * transpose=1 writes [K][N] instead (the dgrad operand).  out[n][p * C + c] = w[n][c * PP + p] with C = chw_c,
+ * PP = K / C; chw_c > 0 with K % chw_c != 0 is refused with SFOD_EBADARG before any launch (pack and unpack). */
 int sfod_pack_fc_weight(const float* w, void* out, int N, int K, int chw_c, int transpose, int dt,
                         void* stream);
 int sfod_unpack_fc_wgrad(const float* dw_packed, float* dw, int N, int K, int chw_c,
@@ -917,6 +918,9 @@ int sfod_cast_pairs_both(const float* src, void* dst_f16x3, void* dst_bf16x3, in
 int sfod_f16x3_poll(uint32_t* word, void* stream);
 /* utilities */
 int sfod_fill_f32(float* p, int64_t n, float v, void* stream);
+/* src (src_dt) -> dst (dst_dt), n logical elements.  Served: SFOD_F32 <-> SFOD_BF16 and the two copies; SFOD_F32 <-> either
+ * pair format, pair -> the same pair, pair -> the other pair (the re-split of fp32(hi + lo)); pairs need n % 8 == 0.
+ * Anything else -- an unknown storage type, SFOD_BF16 <-> a pair format -- is refused with SFOD_EBADARG before any launch. */
 int sfod_cast(const void* src, void* dst, int64_t n, int src_dt, int dst_dt, void* stream);
 
 #ifdef __cplusplus

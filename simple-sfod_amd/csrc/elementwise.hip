@@ -1905,6 +1905,7 @@ extern "C" int sfod_pack_fc_weight_ld_ws(const float* w, void* out, uint32_t* ab
   SFOD_REQUIRE(ld >= (transpose ? N : K), "pack_fc_weight: ld too small");
   SFOD_REQUIRE(!sfod_is_pairs(dt) || ld % 8 == 0, "pack_fc_weight: operand pairs need ld % 8 == 0");
   SFOD_REQUIRE(absmax == nullptr || dt == SFOD_F16X3, "pack_fc_weight: the per-tensor scale belongs to SFOD_F16X3");
+  SFOD_REQUIRE(chw_c == 0 || K % chw_c == 0, "pack_fc_weight: K is not a multiple of chw_c");
   hipStream_t s = (hipStream_t)stream;
   if (absmax != nullptr) {
     const int rc = launch_weight_absmax(w, (int64_t)N * K, nullptr, 1, absmax, s);
@@ -1990,6 +1991,7 @@ k_unpack_fc_chw(const float* __restrict__ dwp, float* __restrict__ dw, int C, in
 extern "C" int sfod_unpack_fc_wgrad_ld(const float* dw_packed, float* dw, int N, int K, int chw_c, int ld,
                                        int accumulate, void* stream) {
   SFOD_REQUIRE_EXTENTS("unpack_fc_wgrad_ld", N, K, chw_c, ld);
+  SFOD_REQUIRE(chw_c == 0 || K % chw_c == 0, "unpack_fc_wgrad: K is not a multiple of chw_c");
   if (chw_c > 0 && K % chw_c == 0 && K / chw_c <= 64 && (int64_t)N * K >= (1 << 20)) {
     const int C = chw_c, PP = K / chw_c;
     hipLaunchKernelGGL(k_unpack_fc_chw, dim3(cdiv(C, 64), N), dim3(256), (size_t)64 * PP * 4, (hipStream_t)stream,
@@ -2501,6 +2503,8 @@ extern "C" int sfod_cast_pairs_both(const float* src, void* dst_f16x3, void* dst
 
 extern "C" int sfod_cast(const void* src, void* dst, int64_t n, int src_dt, int dst_dt, void* stream) {
   SFOD_REQUIRE(sfod_i64s_ok({n}), "cast: negative or oversized extent");
+  SFOD_REQUIRE(src_dt >= SFOD_F32 && src_dt <= SFOD_F16X3 && dst_dt >= SFOD_F32 && dst_dt <= SFOD_F16X3,
+               "cast: unknown storage type");
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(ew_grid(n)), b(256);
@@ -2527,8 +2531,10 @@ extern "C" int sfod_cast(const void* src, void* dst, int64_t n, int src_dt, int 
     hipLaunchKernelGGL((k_cast<bf16_t, float>), g, b, 0, s, (const bf16_t*)src, (float*)dst, n);
   else if (src_dt == SFOD_F32 && dst_dt == SFOD_F32)
     hipLaunchKernelGGL((k_cast<float, float>), g, b, 0, s, (const float*)src, (float*)dst, n);
-  else
+  else if (src_dt == SFOD_BF16 && dst_dt == SFOD_BF16)
     hipLaunchKernelGGL((k_cast<bf16_t, bf16_t>), g, b, 0, s, (const bf16_t*)src, (bf16_t*)dst, n);
+  else
+    SFOD_REQUIRE(false, "cast: plain tensors convert between fp32 and bf16 only");
   return sfod_check_launch("cast");
 }
 
