@@ -549,6 +549,12 @@ int sfod_roi_match_opt(const float* boxes, const int32_t* box_count, int B, int 
  *   ascending then bg ascending, out_count [B]. */
 int sfod_subsample(void* labels_or_cls, const uint32_t* keys, int B, int n, int num, float pos_frac,
                    int bg_label, int mode, int32_t* out_idx, int32_t* out_count, void* stream);
+/* The same with the positive quota given as a count.  d2 evaluates int(num * positive_fraction) in double; the fp32 product of
+ * the fraction rounded to fp32, which sfod_subsample takes, is one less for some pairs (300 * 0.21: 63 against 62), so a caller
+ * that holds the configured fraction computes the count itself.  0 <= pos_quota <= num, else SFOD_EBADARG.  sfod_subsample is
+ * this call with pos_quota = (int)((float)num * pos_frac); it refuses a pos_frac outside [0, 1] (NaN included). */
+int sfod_subsample_quota(void* labels_or_cls, const uint32_t* keys, int B, int n, int num, int pos_quota,
+                         int bg_label, int mode, int32_t* out_idx, int32_t* out_count, void* stream);
 
 /* ---- K11: RPN losses (Appendix A.10; rpn.py:46-49).  loss[0]=loss_rpn_cls, loss[1]=
  * loss_rpn_loc, both / (batch_per_image*B).  With grad_scale != NULL (device fp32 [2], the

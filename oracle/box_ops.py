@@ -157,11 +157,12 @@ def subsample_labels(labels, num_samples, positive_fraction, bg_label, keys):
     neg = torch.nonzero(labels == bg_label).squeeze(1)
     num_pos = min(pos.numel(), int(num_samples * positive_fraction))
     num_neg = min(neg.numel(), num_samples - num_pos)
-    keys = keys.to(torch.int64)
+    keys = keys.to(torch.int64) % (1 << 32)          # uint32 keys, also when they arrive as int32 bit patterns
 
     def pick(cand, n):
-        k = keys[cand] * (1 << 32) + cand
-        order = torch.argsort(k)
+        # cand ascends, so a stable sort by key is the (key, index) order (key * 2^32 + index would overflow int64 for
+        # keys >= 2^31)
+        order = torch.argsort(keys[cand], stable=True)
         return cand[order[:n]].sort().values
 
     return pick(pos, num_pos), pick(neg, num_neg)

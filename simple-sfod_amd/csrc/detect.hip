@@ -953,7 +953,7 @@ __device__ bool select_threshold_hist(const void* lab, const uint32_t* keys, int
 
 template <int MODE>
 __global__ void __launch_bounds__(SS_THREADS)
-k_subsample(void* lab, const uint32_t* __restrict__ keys, int n, int num, float pos_frac, int bg,
+k_subsample(void* lab, const uint32_t* __restrict__ keys, int n, int num, int pos_quota, int bg,
             int32_t* __restrict__ out_idx, int32_t* __restrict__ out_count) {
   __shared__ int red[SS_THREADS / 64];
   __shared__ int hist[SS_BINS];
@@ -971,7 +971,7 @@ k_subsample(void* lab, const uint32_t* __restrict__ keys, int n, int num, float 
   }
   cpos = block_sum_i(cpos, red);
   cneg = block_sum_i(cneg, red);
-  const int num_pos = min(cpos, (int)((float)num * pos_frac));
+  const int num_pos = min(cpos, pos_quota);
   const int num_neg = min(cneg, num - num_pos);
   uint64_t Tpos = ~0ull, Tneg = ~0ull;
   if (num_pos < cpos && num_pos > 0) {
@@ -1019,18 +1019,31 @@ k_subsample(void* lab, const uint32_t* __restrict__ keys, int n, int num, float 
   if (threadIdx.x == 0) out_count[b] = num_pos + num_neg;
 }
 
+// pos_quota = int(num * positive_fraction), the count d2's subsample_labels evaluates in double: the caller computes it from
+// the configured fraction, so no rounding of the fraction to fp32 can move it (300 * 0.21 is 63 in double, 62 in fp32)
+extern "C" int sfod_subsample_quota(void* labels_or_cls, const uint32_t* keys, int B, int n, int num,
+                                    int pos_quota, int bg_label, int mode, int32_t* out_idx, int32_t* out_count,
+                                    void* stream) {
+  SFOD_REQUIRE_EXTENTS("subsample", B, n, num, pos_quota);
+  SFOD_REQUIRE(n >= 1 && n < (1 << 24), "subsample n");
+  SFOD_REQUIRE(pos_quota <= num, "subsample: the positive quota exceeds num");
+  if (mode == 0)
+    hipLaunchKernelGGL(k_subsample<0>, dim3(B), dim3(SS_THREADS), 0, (hipStream_t)stream, labels_or_cls,
+                       keys, n, num, pos_quota, bg_label, out_idx, out_count);
+  else
+    hipLaunchKernelGGL(k_subsample<1>, dim3(B), dim3(SS_THREADS), 0, (hipStream_t)stream, labels_or_cls,
+                       keys, n, num, pos_quota, bg_label, out_idx, out_count);
+  return sfod_check_launch("subsample");
+}
+
+// the quota as the fp32 product of an fp32 fraction (what this entry point has always computed)
 extern "C" int sfod_subsample(void* labels_or_cls, const uint32_t* keys, int B, int n, int num,
                               float pos_frac, int bg_label, int mode, int32_t* out_idx, int32_t* out_count,
                               void* stream) {
   SFOD_REQUIRE_EXTENTS("subsample", B, n, num);
-  SFOD_REQUIRE(n >= 1 && n < (1 << 24), "subsample n");
-  if (mode == 0)
-    hipLaunchKernelGGL(k_subsample<0>, dim3(B), dim3(SS_THREADS), 0, (hipStream_t)stream, labels_or_cls,
-                       keys, n, num, pos_frac, bg_label, out_idx, out_count);
-  else
-    hipLaunchKernelGGL(k_subsample<1>, dim3(B), dim3(SS_THREADS), 0, (hipStream_t)stream, labels_or_cls,
-                       keys, n, num, pos_frac, bg_label, out_idx, out_count);
-  return sfod_check_launch("subsample");
+  const float q = (float)num * pos_frac;
+  SFOD_REQUIRE(q >= 0.f && q <= (float)num, "subsample: pos_frac must be in [0, 1]");
+  return sfod_subsample_quota(labels_or_cls, keys, B, n, num, (int)q, bg_label, mode, out_idx, out_count, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

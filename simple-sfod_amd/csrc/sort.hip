@@ -14,8 +14,10 @@
 
 static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
-// -0.0 is canonicalised to +0.0 like torch's compare
+// -0.0 is canonicalised to +0.0 like torch's compare; every NaN, whatever its sign, ranks above +inf (torch.sort puts
+// all NaNs first in descending order, equal among themselves, so the original index orders them)
 __device__ __forceinline__ uint32_t f32_orderable(float f) {
+  if (f != f) return 0xffffffffu;
   f = f + 0.0f;
   const uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);

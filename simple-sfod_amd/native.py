@@ -1415,10 +1415,18 @@ def roi_match(boxes, box_count, gt_boxes, gt_classes, gt_count, thr, num_classes
     return matched, cls
 
 
+def positive_quota(num, pos_frac):
+    """``int(num * positive_fraction)`` in double, as d2's subsample_labels evaluates it from the configured values"""
+    q = int(num * float(pos_frac))
+    if not 0 <= q <= num:
+        raise ValueError(f"POSITIVE_FRACTION {pos_frac} of BATCH_SIZE_PER_IMAGE {num}: the positive quota {q} is outside [0, {num}]")
+    return q
+
+
 def subsample_rpn_(labels, keys, num, pos_frac):
     B, n = labels.shape
     counts = torch.empty(B, 2, dtype=torch.int32, device=labels.device)
-    call("sfod_subsample", labels, keys, B, n, num, float(pos_frac), 0, 0, None, counts)
+    call("sfod_subsample_quota", labels, keys, B, n, num, positive_quota(num, pos_frac), 0, 0, None, counts)
     return labels, counts
 
 
@@ -1426,7 +1434,7 @@ def subsample_roi(cls, keys, num, pos_frac, bg_label):
     B, n = cls.shape
     idx = torch.zeros(B, num, dtype=torch.int32, device=cls.device)
     cnt = torch.empty(B, dtype=torch.int32, device=cls.device)
-    call("sfod_subsample", cls, keys, B, n, num, float(pos_frac), bg_label, 1, idx, cnt)
+    call("sfod_subsample_quota", cls, keys, B, n, num, positive_quota(num, pos_frac), bg_label, 1, idx, cnt)
     return idx, cnt
 
 

@@ -628,8 +628,9 @@ def test_nms_progressive_phases_mixed_images(native):
 
 @pytest.mark.parametrize("n", [2, 100, 9990, 16000, 16384, 16385, 20000, 30720, 34200, 98304, 131072])
 def test_segmented_sort_stable_descending_with_ties(native, n):
-    """LDS bitonic sort (n <= 16384) and the chunk-sort + merge-path passes above it: order identical to
-    torch.sort(descending=True, stable=True), incl. heavy ties, +-0.0, -inf / +inf."""
+    """LDS bitonic sort in one workgroup (n <= 4096) and the chunk-sort + merge-path passes above it (4096-key chunks at
+    these sizes): order identical to torch.sort(descending=True, stable=True), incl. heavy ties, +-0.0, -inf / +inf.
+    The path switches themselves (4096 | 4097, 131072 | 131073) and NaN keys: tests/test_gpu_detection_decisions.py."""
     g = torch.Generator().manual_seed(n)
     B = 3
     scores = torch.randn(B, n, generator=g)

@@ -149,8 +149,8 @@ def test_defaults_make_the_calls_they_made_before(sfod, monkeypatch):
     _drive(sfod, _rpn(sfod, cfg), _heads(sfod, cfg))
     names = [c[0] for c in calls]
     assert names == ["sfod_rpn_decode", "sfod_segmented_sort_desc", "sfod_rpn_gather_topk", "sfod_nms", "sfod_gather_kept",
-                     "sfod_anchor_match", "sfod_subsample", "sfod_rpn_loss", "sfod_rpn_loss",
-                     "sfod_append_gt", "sfod_roi_match", "sfod_subsample", "sfod_roi_build_samples"]
+                     "sfod_anchor_match", "sfod_subsample_quota", "sfod_rpn_loss", "sfod_rpn_loss",
+                     "sfod_append_gt", "sfod_roi_match", "sfod_subsample_quota", "sfod_roi_build_samples"]
     by = dict(calls)
     A = 15
     assert by["sfod_rpn_decode"] == [80, A, 2, 10, 9, 16]                                   # ld, A, B, Hf, Wf, stride
@@ -165,8 +165,9 @@ def test_options_reach_the_general_entry_points(sfod, monkeypatch):
     _drive(sfod, _rpn(sfod, cfg), _heads(sfod, cfg))
     names = [c[0] for c in calls]
     assert names == ["sfod_rpn_decode_shift", "sfod_segmented_sort_desc", "sfod_rpn_gather_topk_opt", "sfod_nms",
-                     "sfod_gather_kept", "sfod_anchor_match_opt", "sfod_subsample", "sfod_rpn_loss_shift",
-                     "sfod_rpn_loss_shift", "sfod_append_gt", "sfod_roi_match_opt", "sfod_subsample", "sfod_roi_build_samples"]
+                     "sfod_gather_kept", "sfod_anchor_match_opt", "sfod_subsample_quota", "sfod_rpn_loss_shift",
+                     "sfod_rpn_loss_shift", "sfod_append_gt", "sfod_roi_match_opt", "sfod_subsample_quota",
+                     "sfod_roi_build_samples"]
     by = dict(calls)
     assert by["sfod_rpn_decode_shift"][-5:] == [1.0, 1.0, 1.0, 1.0, 8.0]                    # weights, shift
     assert by["sfod_rpn_gather_topk_opt"][-1] == 8.0                                         # min_size
