@@ -325,6 +325,32 @@ int sfod_bn_finalize(const float* stats, int nblocks, int M, int C,
  * statistics (k forward passes over the same batch between two optimiser steps -- the reference's student runs its
  * backbone three times per step when its zero-weighted domain branch is on, source_free_adaptive_teacher.py:527-537).
  * num_batches_tracked: the BatchNorm buffer of that name (device int64 scalar), incremented by k; may be NULL. */
+/* `stats` (written by the convolution's epilogue, nblocks * (2 * C + 1) floats): stats[blk][0][c] = the block's sum over its
+ * rows, stats[blk][1][c] = the block's sum of squared deviations from ITS mean, then -- behind all the sums, at
+ * stats + nblocks * 2 * C -- counts[blk] = the block's rows as a float; a block with count 0 is skipped. */
+/* Population statistics (TEST.PRECISE_BN, AdaBN with precise=True): sfod_bn_finalize with one more operand.  `pop` is the
+ * layer's accumulator, three rows of fp64 `pop_stride` doubles apart -- pop[c] = n, pop[pop_stride + c] = mean,
+ * pop[2 * pop_stride + c] = M2 = sum (x - mean)^2 over everything seen so far -- so that all layers of a model can be columns
+ * of one [3][sum C] tensor.  With pop != NULL the SAME launch that writes mean / invstd (bit-identical to sfod_bn_finalize's)
+ * merges this batch (M, mu_b = sum x / M, tot = sum (x - mu_b)^2, both already held in fp64) by Chan's update
+ *   d = mu_b - mean;  n' = n + M;  mean += d M / n';  M2 += tot + d^2 n M / n'
+ * leaves running_mean / running_var alone and adds 1 to num_batches_tracked (whatever update_running says).  No further
+ * launch, no atomics: one thread owns a channel.  pop == NULL is sfod_bn_finalize.  SFOD_EBADARG before any launch: pop not
+ * 8-byte aligned, pop_stride <= 0 or < C. */
+int sfod_bn_finalize_pop(const float* stats, int nblocks, int M, int C,
+                         float* mean, float* invstd, float* running_mean, float* running_var,
+                         float momentum, float eps, int update_running, int64_t* num_batches_tracked,
+                         float* ws, double* pop, int64_t pop_stride, void* stream);
+/* The accumulated statistics of every layer into their running buffers in ONE launch: running_mean = fp32(mean),
+ * running_var = fp32(M2 / n) (biased; fp64 with one rounding).  `table` (device, int64) and `table_host` (the same values
+ * on the host, read by the checks only): n <= 1024 entries of 4 values {first column, C, running_mean pointer,
+ * running_var pointer}.  A layer with n = 0 (it never ran) keeps its buffers.  SFOD_EBADARG before any launch: pop NULL
+ * or misaligned, pop_stride <= 0, an entry with first column + C > pop_stride or a NULL / misaligned buffer. */
+int sfod_bn_pop_commit(const double* pop, int64_t pop_stride, const int64_t* table, const int64_t* table_host, int n,
+                       void* stream);
+/* dst <- Chan merge of two contiguous [3][columns] accumulators, column by column (dst first: merging the ranks'
+ * accumulators in rank order gives every rank the same bits).  Columns with src n = 0 are left alone. */
+int sfod_bn_pop_merge(double* dst, const double* src, int64_t columns, void* stream);
 /* Layers whose statistics fit one slice (nblocks <= 64) are finalised by ONE launch instead of two (default 1; environment
  * SFOD_BN_FINALIZE_FUSED): the same sums in the same order, bit-identical outputs.  0 keeps the two launches (A/B runs, the
  * parity test). */

@@ -446,6 +446,10 @@ def add_native_config(cfg):
     _C.SFOD.FUSE_BN_INPUT = True
     # d2's EvalHook inside Trainer.train(): Trainer.test every TEST.EVAL_PERIOD iterations and after the last one
     _C.SFOD.EVAL_HOOK = True
+    # TEST.PRECISE_BN under several ranks.  False: every rank keeps the population statistics of its own share (the
+    # reference's DDP runs with broadcast_buffers=False); True: the ranks' accumulators are gathered and merged in rank
+    # order before the commit, every rank holds the statistics of the union (engine/precise_bn.py)
+    _C.SFOD.PRECISE_BN = CN({"SYNC": False})
     # the evaluators of Trainer.test, by name: "coco" (NewCOCOEvaluator), "f1" (F1Evaluator, counted on the device)
     _C.SFOD.EVALUATORS = ("coco",)
     # json file {"<dataset name>": {"json_file": ..., "image_root": ...}}: COCO-format datasets for the names in

@@ -465,6 +465,27 @@ extern "C" int sfod_resize_bilinear_u8(const void* src, void* dst, int C, int H,
 // ---------------------------------------------------------------------------------------------
 #define BNF_SPLITS 64
 
+// Population accumulator of a BatchNorm layer (sfod_bn_finalize_pop): per channel (n, mean, M2) in fp64, rows `stride`
+// doubles apart.  Chan's update with a batch of `nb` elements, mean `mub` and centred square sum `m2b`; the three finalize
+// forms and k_bn_pop_merge all go through THIS function (contraction off: the same roundings wherever it is inlined).
+__device__ __forceinline__ void bn_pop_update(double* __restrict__ pop, long long stride, int c, double nb, double mub,
+                                              double m2b) {
+#pragma clang fp contract(off)
+  if (!(nb > 0.0)) return;
+  const double n = pop[c], mean = pop[stride + c], m2 = pop[2 * stride + c];
+  if (!(n > 0.0)) {                 // the first batch is taken as it is (mub * nb / nb need not be mub)
+    pop[c] = nb;
+    pop[stride + c] = mub;
+    pop[2 * stride + c] = m2b;
+    return;
+  }
+  const double d = mub - mean;
+  const double nn = n + nb;
+  pop[c] = nn;
+  pop[stride + c] = mean + d * nb / nn;
+  pop[2 * stride + c] = m2 + (m2b + d * d * n * nb / nn);
+}
+
 __global__ void __launch_bounds__(1024)
 k_bn_partial(const float* __restrict__ stats, int nblocks, int C, double* __restrict__ part) {
   // 16 waves split the blocks of this slice; lanes are consecutive channels (coalesced rows)
@@ -499,9 +520,11 @@ k_bn_partial(const float* __restrict__ stats, int nblocks, int C, double* __rest
 __global__ void __launch_bounds__(256)
 k_bn_final(const double* __restrict__ part, int nsplit, int M, int C, float* __restrict__ mean,
            float* __restrict__ invstd, float* __restrict__ rmean, float* __restrict__ rvar, float momentum,
-           float eps, int update_running, long long* __restrict__ nbt) {
+           float eps, int update_running, long long* __restrict__ nbt, double* __restrict__ pop,
+           long long pop_stride) {
   __shared__ double red[4][3][64];
-  if (nbt != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *nbt += update_running;   // BatchNorm's num_batches_tracked
+  // BatchNorm's num_batches_tracked (a population pass counts once and moves no running statistic)
+  if (nbt != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *nbt += pop != nullptr ? 1 : update_running;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane;
   double a = 0.0, q = 0.0, m2 = 0.0;
@@ -523,7 +546,9 @@ k_bn_final(const double* __restrict__ part, int nsplit, int M, int C, float* __r
   const double var = tot / (double)M;
   mean[c] = (float)mu;
   invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (update_running) {
+  if (pop != nullptr) {
+    bn_pop_update(pop, pop_stride, c, (double)M, mu, tot);
+  } else if (update_running) {
     // update_running = k >= 1 momentum updates with the SAME batch statistics folded into this call (k forward passes
     // over one batch between two optimiser steps), each rounded to fp32 like k separate BatchNorm calls
     const double unbiased = (M > 1) ? tot / (double)(M - 1) : var;
@@ -544,9 +569,10 @@ k_bn_final(const double* __restrict__ part, int nsplit, int M, int C, float* __r
 __global__ void __launch_bounds__(1024)
 k_bn_finalize_one(const float* __restrict__ stats, int nblocks, int M, int C, float* __restrict__ mean,
                   float* __restrict__ invstd, float* __restrict__ rmean, float* __restrict__ rvar, float momentum,
-                  float eps, int update_running, long long* __restrict__ nbt) {
+                  float eps, int update_running, long long* __restrict__ nbt, double* __restrict__ pop,
+                  long long pop_stride) {
   __shared__ double red[16][3][64];
-  if (nbt != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *nbt += update_running;
+  if (nbt != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *nbt += pop != nullptr ? 1 : update_running;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane;
   const float* counts = stats + (int64_t)nblocks * 2 * C;
@@ -583,7 +609,9 @@ k_bn_finalize_one(const float* __restrict__ stats, int nblocks, int M, int C, fl
   const double var = tot / (double)M;
   mean[c] = (float)mu;
   invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (update_running) {
+  if (pop != nullptr) {
+    bn_pop_update(pop, pop_stride, c, (double)M, mu, tot);
+  } else if (update_running) {
     const double unbiased = (M > 1) ? tot / (double)(M - 1) : var;
     float rm = rmean[c], rv = rvar[c];
     for (int k = 0; k < update_running; ++k) {
@@ -604,28 +632,102 @@ extern "C" int sfod_bn_finalize_ws_floats(int C) {
   return BNF_SPLITS * 3 * C * 2;
 }
 
-extern "C" int sfod_bn_finalize(const float* stats, int nblocks, int M, int C,
-                                float* mean, float* invstd, float* running_mean, float* running_var,
-                                float momentum, float eps, int update_running, int64_t* num_batches_tracked,
-                                float* ws, void* stream) {
+extern "C" int sfod_bn_finalize_pop(const float* stats, int nblocks, int M, int C,
+                                    float* mean, float* invstd, float* running_mean, float* running_var,
+                                    float momentum, float eps, int update_running, int64_t* num_batches_tracked,
+                                    float* ws, double* pop, int64_t pop_stride, void* stream) {
   SFOD_REQUIRE_EXTENTS("bn_finalize", nblocks, M, C);
   SFOD_REQUIRE(ws != nullptr && ((uintptr_t)ws & 7) == 0, "bn_finalize: 8-byte aligned workspace required");
+  if (pop != nullptr) {
+    SFOD_REQUIRE(((uintptr_t)pop & 7) == 0, "bn_finalize_pop: 8-byte aligned accumulator required");
+    SFOD_REQUIRE(pop_stride > 0 && pop_stride >= C && pop_stride <= (1LL << 40),
+                 "bn_finalize_pop: the accumulator's row stride must be positive and hold C columns");
+  }
   hipStream_t s = (hipStream_t)stream;
   int nsplit = (nblocks + 63) / 64;   // >= 64 blocks (4 per wave) per slice
   if (nsplit > BNF_SPLITS) nsplit = BNF_SPLITS;
   if (nsplit < 1) nsplit = 1;
+  long long* nbt = (update_running || pop != nullptr) ? (long long*)num_batches_tracked : (long long*)nullptr;
   if (nsplit == 1 && bn_finalize_fused()) {
     hipLaunchKernelGGL(k_bn_finalize_one, dim3(cdiv(C, 64)), dim3(1024), 0, s, stats, nblocks, M, C, mean, invstd,
-                       running_mean, running_var, momentum, eps, update_running,
-                       update_running ? (long long*)num_batches_tracked : (long long*)nullptr);
+                       running_mean, running_var, momentum, eps, update_running, nbt, pop, (long long)pop_stride);
     return sfod_check_launch("bn_finalize");
   }
   double* part = reinterpret_cast<double*>(ws);
   hipLaunchKernelGGL(k_bn_partial, dim3(cdiv(C, 64), nsplit), dim3(1024), 0, s, stats, nblocks, C, part);
   hipLaunchKernelGGL(k_bn_final, dim3(cdiv(C, 64)), dim3(256), 0, s, part, nsplit, M, C, mean, invstd,
-                     running_mean, running_var, momentum, eps, update_running,
-                     update_running ? (long long*)num_batches_tracked : (long long*)nullptr);
+                     running_mean, running_var, momentum, eps, update_running, nbt, pop, (long long)pop_stride);
   return sfod_check_launch("bn_finalize");
+}
+
+extern "C" int sfod_bn_finalize(const float* stats, int nblocks, int M, int C,
+                                float* mean, float* invstd, float* running_mean, float* running_var,
+                                float momentum, float eps, int update_running, int64_t* num_batches_tracked,
+                                float* ws, void* stream) {
+  return sfod_bn_finalize_pop(stats, nblocks, M, C, mean, invstd, running_mean, running_var, momentum, eps, update_running,
+                              num_batches_tracked, ws, nullptr, 0, stream);
+}
+
+// Every layer's population statistics into its running buffers in ONE launch (table-driven like k_pack_conv_weights_multi):
+// entry blockIdx.x = {first column, C, running_mean*, running_var*}.  running_mean = fp32(mean), running_var = fp32(M2 / n):
+// fp64 throughout, one rounding.  A layer that never ran (n = 0) keeps its buffers; an entry that leaves the accumulator's
+// columns is skipped here as well (the host refuses it first).
+#define BNPOP_MAX_LAYERS 1024
+__global__ void __launch_bounds__(256)
+k_bn_pop_commit(const double* __restrict__ pop, long long stride, const long long* __restrict__ table) {
+  const long long* e = table + (long long)blockIdx.x * 4;
+  const long long off = e[0], C = e[1];
+  if (off < 0 || C < 0 || off > stride || C > stride - off) return;
+  float* rmean = reinterpret_cast<float*>(e[2]);
+  float* rvar = reinterpret_cast<float*>(e[3]);
+  for (long long c = threadIdx.x; c < C; c += blockDim.x) {
+    const double n = pop[off + c];
+    if (!(n > 0.0)) continue;
+    rmean[c] = (float)pop[stride + off + c];
+    rvar[c] = (float)(pop[2 * stride + off + c] / n);
+  }
+}
+
+extern "C" int sfod_bn_pop_commit(const double* pop, int64_t pop_stride, const int64_t* table, const int64_t* table_host,
+                                  int n, void* stream) {
+  SFOD_REQUIRE_EXTENTS("bn_pop_commit", n);
+  SFOD_REQUIRE(n <= BNPOP_MAX_LAYERS, "bn_pop_commit: more than 1024 table entries");
+  SFOD_REQUIRE(pop != nullptr && ((uintptr_t)pop & 7) == 0, "bn_pop_commit: 8-byte aligned accumulator required");
+  SFOD_REQUIRE(pop_stride > 0 && pop_stride <= (1LL << 40), "bn_pop_commit: the accumulator's row stride must be positive");
+  if (n == 0) return 0;
+  SFOD_REQUIRE(table != nullptr && table_host != nullptr && ((uintptr_t)table & 7) == 0 && ((uintptr_t)table_host & 7) == 0,
+               "bn_pop_commit: the table is needed on the device and (for these checks) on the host");
+  for (int i = 0; i < n; ++i) {
+    const int64_t off = table_host[4 * i], C = table_host[4 * i + 1];
+    SFOD_REQUIRE(off >= 0 && C >= 0 && off <= pop_stride && C <= pop_stride - off,
+                 "bn_pop_commit: a table entry runs past the accumulator's columns");
+    SFOD_REQUIRE(C == 0 || (table_host[4 * i + 2] != 0 && table_host[4 * i + 3] != 0 &&
+                            ((table_host[4 * i + 2] | table_host[4 * i + 3]) & 3) == 0),
+                 "bn_pop_commit: a table entry without (aligned) running buffers");
+  }
+  hipLaunchKernelGGL(k_bn_pop_commit, dim3(n), dim3(256), 0, (hipStream_t)stream, pop, (long long)pop_stride,
+                     (const long long*)table);
+  return sfod_check_launch("bn_pop_commit");
+}
+
+// dst <- Chan merge of dst and src, two [3][columns] accumulators, elementwise over the columns (the ranks' accumulators
+// merged in rank order).  A column src never saw (n = 0) leaves dst as it is.
+__global__ void __launch_bounds__(256)
+k_bn_pop_merge(double* __restrict__ dst, const double* __restrict__ src, long long columns) {
+  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= columns) return;
+  bn_pop_update(dst + c, columns, 0, src[c], src[columns + c], src[2 * columns + c]);
+}
+
+extern "C" int sfod_bn_pop_merge(double* dst, const double* src, int64_t columns, void* stream) {
+  SFOD_REQUIRE(columns >= 0 && columns <= (1LL << 30), "bn_pop_merge: negative or oversized column count");
+  if (columns == 0) return 0;
+  SFOD_REQUIRE(dst != nullptr && src != nullptr && (((uintptr_t)dst | (uintptr_t)src) & 7) == 0,
+               "bn_pop_merge: 8-byte aligned accumulators required");
+  SFOD_REQUIRE(dst != src, "bn_pop_merge: dst and src must differ");
+  hipLaunchKernelGGL(k_bn_pop_merge, dim3(cdiv(columns, 256)), dim3(256), 0, (hipStream_t)stream, dst, src,
+                     (long long)columns);
+  return sfod_check_launch("bn_pop_merge");
 }
 
 // ---------------------------------------------------------------------------------------------

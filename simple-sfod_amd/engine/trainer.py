@@ -395,6 +395,40 @@ class BaseTrainer:
         self.iter = 0
         self.storage = EventStorage(0)
         self.model.train()
+        self._build_precise_bn(cfg)
+
+    def _build_precise_bn(self, cfg):
+        """d2 ``hooks.PreciseBN(cfg.TEST.EVAL_PERIOD, self.model, self.build_train_loader(cfg), NUM_ITER)`` of every reference
+        trainer's ``build_hooks`` (base.py:237-245), built only when TEST.PRECISE_BN.ENABLED and the model has BatchNorm
+        layers in training mode: a second train loader ("a new data loader to not affect training": its own sampler and
+        generators, no worker processes here), whose iterator is created at the first update and goes on from period to
+        period.  ``self.model`` is the student of the teacher-student trainers; the teacher gets the statistics by the EMA."""
+        self._precise_bn_loader = self._precise_bn_iter = None
+        pb = cfg.TEST.PRECISE_BN
+        if not pb.ENABLED:
+            return
+        from .precise_bn import get_bn_modules, validate_num_iter
+        validate_num_iter(pb.NUM_ITER)
+        if get_bn_modules(self.model):
+            self._precise_bn_loader = self.build_train_loader(cfg)
+
+    def _do_precise_bn(self):
+        """The update itself.  It is timed between two device synchronisations and the writer's mark is moved on by that
+        time, so that none of it enters the ``time`` scalar (an evaluation inside a writer period is counted there)."""
+        from .precise_bn import update_bn_stats
+        if self._precise_bn_iter is None:
+            self._precise_bn_iter = iter(self._precise_bn_loader)
+        cuda = torch.device(self.device).type == "cuda"
+        if cuda:
+            torch.cuda.synchronize()
+        start = time.perf_counter()
+        update_bn_stats(self.model, self._precise_bn_iter, self.cfg.TEST.PRECISE_BN.NUM_ITER,
+                        sync=bool(self.cfg.SFOD.PRECISE_BN.SYNC))
+        if cuda:
+            torch.cuda.synchronize()
+        mark = self.__dict__.get("_writer_mark")
+        if mark is not None:
+            self._writer_mark = (mark[0] + (time.perf_counter() - start), mark[1])
 
     def _broadcast_initial_state(self):
         """DDP's constructor broadcast: every rank starts from rank 0's parameters and buffers -- also after loading
@@ -572,6 +606,12 @@ class BaseTrainer:
         # d2 stamps a scalar with the iteration it was put in (TrainerBase.before_step: ``storage.iter = self.iter``; JSONWriter
         # writes that number): the last record of a 4-iteration run says ``"iteration": 3``
         self.storage.iter = self.iter
+        # PreciseBN(cfg.TEST.EVAL_PERIOD, ...): before the checkpointer, so that this iteration's checkpoint holds the population
+        # statistics; its own period rule, whatever SFOD.EVAL_HOOK says
+        if self.__dict__.get("_precise_bn_loader") is not None:
+            from .precise_bn import precise_bn_due
+            if precise_bn_due(nxt, self.max_iter, self.cfg.TEST.EVAL_PERIOD):
+                self._do_precise_bn()
         # PeriodicCheckpointer: every CHECKPOINT_PERIOD iterations, and ``model_final`` after the last one (what
         # the reference's eval / AdaBN configs point MODEL.WEIGHTS at)
         p = self.cfg.SOLVER.CHECKPOINT_PERIOD
@@ -804,6 +844,7 @@ class SourceFreeAdaptiveTeacherTrainer(BaseTrainer):
         if self.elide and cfg.DOMAIN_CLASSIFIER.ENABLED and not dc_live and not cfg.WEAK_STRONG_AUGMENT \
                 and hasattr(self.model.backbone, "bn_updates_per_forward"):
             self._elided_bn_updates = 3
+        self._build_precise_bn(cfg)
 
     @staticmethod
     def _frozen(cfg):
@@ -1147,8 +1188,15 @@ def reset_bn_stats(model):
 
 
 @torch.no_grad()
-def adabn_refinement(cfg, model, data_loader, max_iters=1400):
-    """forward-only passes in train mode under no_grad: BN momentum-0.1 running-stat refresh."""
+def adabn_refinement(cfg, model, data_loader, max_iters=1400, precise=False):
+    """forward-only passes in train mode under no_grad: BN momentum-0.1 running-stat refresh.  ``precise``: the same passes
+    through the population accumulator (engine/precise_bn.py) -- the statistics of everything the passes saw, AdaBN's own
+    definition, instead of the momentum tail; nothing to reset."""
+    if precise:
+        from .precise_bn import update_bn_stats
+        model.train()
+        update_bn_stats(model, iter(data_loader), max_iters + 1)
+        return model
     reset_bn_stats(model)
     model.train()
     it = iter(data_loader)
@@ -1164,10 +1212,10 @@ def adabn_refinement(cfg, model, data_loader, max_iters=1400):
     return model
 
 
-def test_refinement(cfg, model, data_loader, max_iters=1400, trainer_cls=None):
+def test_refinement(cfg, model, data_loader, max_iters=1400, trainer_cls=None, precise=False):
     """``base.py:270-315`` as called from ``adabn_refinement`` (:330-337): the statistics passes, then
     ``trainer.test(cfg, model)`` and a ``adabn.pth`` checkpoint in ``OUTPUT_DIR``.  -> test results."""
-    adabn_refinement(cfg, model, data_loader, max_iters)
+    adabn_refinement(cfg, model, data_loader, max_iters, precise=precise)
     results = (trainer_cls or BaseTrainer).test(cfg, model)
     if get_rank() == 0 and cfg.OUTPUT_DIR:
         os.makedirs(cfg.OUTPUT_DIR, exist_ok=True)

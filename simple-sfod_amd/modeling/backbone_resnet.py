@@ -179,6 +179,7 @@ class ResNet(nn.Module):
         self.bn_momentum = 0.1
         self._frozen_gen = 0                 # generation of the frozen stages' values (see _frozen_packed)
         self.bn_updates_per_forward = 1      # see backbone_vgg: momentum updates folded into one forward
+        self.bn_population = None            # see backbone_vgg: {BatchNorm module: accumulator view} during engine/precise_bn.py's passes
         self.fuse_residual = os.environ.get("SFOD_NO_FUSE_RESIDUAL", "0") != "1"   # A/B hook: bn3 + shortcut + ReLU in one pass
         self.dual_join = os.environ.get("SFOD_NO_DUAL_JOIN", "0") != "1"           # A/B hook: join kernels also emit the operand pairs
         self.fuse_stem = os.environ.get("SFOD_NO_FUSE_STEM", "0") != "1"                   # A/B hook: 7x7 stem without the im2col matrix
@@ -312,9 +313,11 @@ class ResNet(nn.Module):
         B, H, W, _ = x.shape
         if self.training:
             y, stats = native.conv_fwd(x, wp, None, conv.out_channels, k, want_stats=True)
+            pop = self.bn_population      # engine/precise_bn.py: population statistics instead of the momentum update
             mean, invstd = native.bn_finalize(stats, B * H * W, conv.out_channels, bn.running_mean, bn.running_var,
                                               self.bn_momentum, bn.eps, self.bn_updates_per_forward,
-                                              num_batches_tracked=bn.num_batches_tracked)
+                                              num_batches_tracked=bn.num_batches_tracked,
+                                              pop=None if pop is None else pop[bn])
         else:
             y = native.conv_fwd(x, wp, None, conv.out_channels, k)
             mean, invstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)

@@ -111,6 +111,9 @@ class vgg_backbone(nn.Module):
         # SFOD.ELIDE_DEAD_BRANCHES only one pass runs and the trainer sets this to 3, which reproduces the side effect
         # exactly: r <- r (1-m)^3 + s (1 - (1-m)^3), num_batches_tracked += 3.
         self.bn_updates_per_forward = 1
+        # set by engine/precise_bn.py for the duration of its passes: train-mode forwards then accumulate population statistics
+        # (sfod_bn_finalize_pop) instead of moving the running ones; None: the usual momentum updates
+        self.bn_population = None
         self.fuse_first = bool(cfg.SFOD.FUSE_FIRST_LAYER) if "SFOD" in cfg and "FUSE_FIRST_LAYER" in cfg.SFOD else True
         self.fuse_bn_input = bool(cfg.SFOD.FUSE_BN_INPUT) if "SFOD" in cfg and "FUSE_BN_INPUT" in cfg.SFOD else True
         self.fuse_bn_input_min_bytes = int(os.environ.get("SFOD_BNIN_MIN_BYTES", str(256 << 20)))
@@ -236,9 +239,12 @@ class vgg_backbone(nn.Module):
         fwd_w, rot_w = self._packed_weights(dt, x.shape[-1], save)
         self._rot_w = rot_w
 
+        pop = self.bn_population      # engine/precise_bn.py: {BatchNorm module: its view of the population accumulator}
+
         def finalize(stats, bn, cout, rows):
             return native.bn_finalize(stats, rows, cout, bn.running_mean, bn.running_var, self.bn_momentum, self.bn_eps,
-                                      self.bn_updates_per_forward, num_batches_tracked=bn.num_batches_tracked)
+                                      self.bn_updates_per_forward, num_batches_tracked=bn.num_batches_tracked,
+                                      pop=None if pop is None else pop[bn])
 
         x_g = native.as_operand(x, self.grad_dtype) if save else None      # conv1_1's weight-gradient operand (8 channels)
         pending = None      # (y, mean, invstd, bn) of the layer below when its BatchNorm + ReLU is left to this layer's conv

@@ -1021,15 +1021,54 @@ def bias_grad(dy, n, db=None, accumulate=False):
 
 
 def bn_finalize(stats, M, C, running_mean, running_var, momentum=0.1, eps=1e-5, update_running=True,
-                num_batches_tracked=None):
+                num_batches_tracked=None, pop=None):
     """``update_running``: False / 0 = no update, True / k = k momentum updates with this batch's statistics;
-    ``num_batches_tracked`` (int64 scalar buffer) is incremented by k in the same launch when given."""
+    ``num_batches_tracked`` (int64 scalar buffer) is incremented by k in the same launch when given.
+    ``pop``: the layer's [3, C] fp64 view of a population accumulator (``bn_pop_accumulator``): this batch is merged into it
+    by the same launch, the running statistics stay and ``num_batches_tracked`` grows by one (sfod_bn_finalize_pop)."""
     mean = torch.empty(C, dtype=torch.float32, device=stats.device)
     invstd = torch.empty_like(mean)
     ws = torch.empty(query("sfod_bn_finalize_ws_floats", C), dtype=torch.float32, device=stats.device)
-    call("sfod_bn_finalize", stats, stats.nblk, M, C, mean, invstd, running_mean, running_var,
-         float(momentum), float(eps), int(update_running), num_batches_tracked, ws)
+    if pop is None:
+        call("sfod_bn_finalize", stats, stats.nblk, M, C, mean, invstd, running_mean, running_var,
+             float(momentum), float(eps), int(update_running), num_batches_tracked, ws)
+        return mean, invstd
+    assert pop.is_cuda and pop.dtype == torch.float64 and tuple(pop.shape) == (3, C) and pop.stride(1) == 1
+    call("sfod_bn_finalize_pop", stats, stats.nblk, M, C, mean, invstd, running_mean, running_var,
+         float(momentum), float(eps), int(update_running), num_batches_tracked, ws, pop.data_ptr(), pop.stride(0))
     return mean, invstd
+
+
+def bn_pop_accumulator(channels, device):
+    """Zeroed population accumulator of a model's BatchNorm layers: one [3, sum C] fp64 tensor (rows n, mean, M2) and each
+    layer's [3, C] column view of it, in the order of ``channels``."""
+    acc = torch.zeros(3, max(int(sum(channels)), 1), dtype=torch.float64, device=device)
+    views, off = [], 0
+    for c in channels:
+        views.append(acc[:, off:off + c])
+        off += c
+    return acc, views
+
+
+def bn_pop_commit(acc, layers):
+    """``layers``: (first column, running_mean, running_var) per layer -> every layer's population mean and biased variance
+    into its running buffers, ONE launch (a layer that never ran keeps its buffers)."""
+    assert acc.is_cuda and acc.dtype == torch.float64 and acc.dim() == 2 and acc.shape[0] == 3 and acc.is_contiguous()
+    rows = []
+    for off, rm, rv in layers:
+        assert rm.dtype == rv.dtype == torch.float32 and rm.is_contiguous() and rv.is_contiguous() and rm.numel() == rv.numel()
+        rows.append([int(off), rm.numel(), rm.data_ptr(), rv.data_ptr()])
+    if not rows:
+        return
+    host = torch.tensor(rows, dtype=torch.int64)
+    call("sfod_bn_pop_commit", acc, acc.stride(0), host.to(acc.device), host.data_ptr(), len(rows))
+
+
+def bn_pop_merge(dst, src):
+    """dst <- Chan merge of two [3, columns] population accumulators (in place, column by column)."""
+    assert dst.shape == src.shape and dst.dtype == src.dtype == torch.float64 and dst.dim() == 2 and dst.shape[0] == 3
+    call("sfod_bn_pop_merge", dst, src, dst.shape[1])
+    return dst
 
 
 def bn_relu_pool_fwd(y, mean, invstd, gamma, beta, pool, relu=True, out_dtype=None, with_grad_operand=False):

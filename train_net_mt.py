@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--num-gpus", type=int, default=1)
     ap.add_argument("--eval-only", action="store_true", help="AdaBN refinement + evaluation (train_net_mt.py:73-82)")
     ap.add_argument("--adabn-iters", type=int, default=1400, help="statistics passes of the refinement (base.py:300)")
+    ap.add_argument("--adabn-precise", action="store_true",
+                    help="--eval-only: population statistics of all passes instead of their momentum-0.1 tail (engine/precise_bn.py)")
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("opts", nargs=argparse.REMAINDER, default=[])
     args = ap.parse_args()
@@ -56,7 +58,8 @@ def main():
         sfod.checkpoint.load_model_weights(model, cfg.MODEL.WEIGHTS)
         loader = sfod.data.TwoCropLoader(cfg, torch.device(cfg.MODEL.DEVICE), rank, world, labeled=True)
         # base.adabn_refinement(cfg, model): reset BN statistics, <= 1400 forward passes, Trainer.test, save "adabn"
-        results = sfod.engine.test_refinement(cfg, model, loader, max_iters=args.adabn_iters, trainer_cls=Trainer)
+        results = sfod.engine.test_refinement(cfg, model, loader, max_iters=args.adabn_iters, trainer_cls=Trainer,
+                                               precise=args.adabn_precise)
         if rank == 0:
             print(results)
         return results
