@@ -507,7 +507,8 @@ int sfod_rpn_decode_shift(const float* rpn_out, int ld, const float* cell_anchor
 int64_t sfod_sort_ws_bytes(int B, int n);
 int sfod_segmented_sort_desc(const float* keys, int B, int n, float* out_keys, int32_t* out_idx,
                              void* ws, int64_t ws_bytes, void* stream);
-/* gather the first k sorted candidates: boxes[b][j] = props[b][idx[b][j]], valid = nonempty */
+/* gather the first k sorted candidates: boxes[b][j] = props[b][idx[b][j]], valid = nonempty and a finite score (d2's
+ * find_top_rpn_proposals drops a candidate whose box or logit is not finite; a non-finite box is empty after the clip) */
 int sfod_rpn_gather_topk(const float* props, const float* sorted_scores, const int32_t* sorted_idx,
                          int B, int NA, int k, float* cand_boxes, float* cand_scores,
                          uint8_t* cand_valid, void* stream);

@@ -246,9 +246,11 @@ __global__ void k_rpn_gather_topk(const float* __restrict__ props, const float* 
   const int idx = sidx[(int64_t)b * NA + j];
   Box bx = load_box(props + ((int64_t)b * NA + idx) * 4);
   store_box(cboxes + ((int64_t)b * k + j) * 4, bx);
-  cscores[(int64_t)b * k + j] = sscores[(int64_t)b * NA + j];
-  // Boxes.nonempty(threshold=min_size): strict
-  cvalid[(int64_t)b * k + j] = ((bx.x2 - bx.x1) > min_size && (bx.y2 - bx.y1) > min_size) ? 1 : 0;
+  const float sc = sscores[(int64_t)b * NA + j];
+  cscores[(int64_t)b * k + j] = sc;
+  // Boxes.nonempty(threshold=min_size): strict.  find_top_rpn_proposals also drops a top-k candidate whose logit is not
+  // finite (NaN and +inf sort first, -inf is inside the top k when k == NA); a non-finite box is already empty after the clip
+  cvalid[(int64_t)b * k + j] = (isfinite(sc) && (bx.x2 - bx.x1) > min_size && (bx.y2 - bx.y1) > min_size) ? 1 : 0;
 }
 
 extern "C" int sfod_rpn_gather_topk_opt(const float* props, const float* sorted_scores,
