@@ -228,6 +228,29 @@ int sfod_conv_first_fused(const void* x, const void* w, const float* bias, const
 int sfod_conv_first_fused_ws(const void* x, const void* w, const uint32_t* w_absmax, const float* bias,
                              const float* scale, const float* shift, void* y, float* stats, int B, int H, int W,
                              int ldy, int act, int dt, void* stream);
+/* The two entry points above run the first-layer kernel at ANY extent (sfod_conv_first_supported says where sfod_conv_fwd
+ * itself picks it, and only there does sfod_conv_stats_blocks give this kernel's count); its statistics are one block per
+ * 8 x 32-pixel tile: sfod_conv_first_stats_blocks (0 for hostile extents).
+ * A/B knobs of the SFOD_BF16X3 / SFOD_F16X3 kernel, same bits at every setting: sfod_set_conv_first_pipe (environment
+ * SFOD_F1_PIPE, default 1) 1 = the pipelined tile loop (next tile's patch in flight, one barrier less per tile, no masks on
+ * full tiles), 0 = the plain loop; sfod_set_conv_first_grid (SFOD_F1_GRID, default 0) n > 0 caps the persistent grid at n
+ * workgroups (tests: several tiles per workgroup on small images), 0 = one workgroup per resident slot. */
+int sfod_conv_first_stats_blocks(int B, int H, int W);
+int sfod_set_conv_first_pipe(int on);
+int sfod_set_conv_first_grid(int n);
+/* Student conv1_1, pass 2 by recomputation: z = relu(bn(conv(x) + bias)) as SFOD_BF16X3 pairs [B,H,W,ldz], BIT-IDENTICAL to
+ * sfod_conv_fwd (fp32 y) followed by sfod_bn_relu_pool_fwd(y, mean, invstd, gamma, beta -> SFOD_BF16X3, ReLU, no pooling):
+ * the same kernel recomputes the K = 27 convolution (reads the 8-channel input instead of the 64-channel y) and its
+ * epilogue is that pass's arithmetic, operation for operation.  y itself still comes from sfod_conv_fwd (the backward
+ * reads it).  _supported: 1 only for Cin = 8, Cout = 64, pool_flags = 0 (no pooling, ReLU: the flags of
+ * sfod_bn_relu_pool_fwd), dt = SFOD_BF16X3, y_dt = SFOD_F32, a shape for which sfod_conv_fwd runs the first-layer kernel,
+ * and the knob below at 1; elsewhere the caller runs sfod_bn_relu_pool_fwd.
+ * sfod_set_first_apply_recompute (environment SFOD_FIRST_APPLY_RECOMPUTE, default 1): A/B knob, 0 = the query refuses. */
+int sfod_conv_first_bn_apply_supported(int B, int H, int W, int Cin, int Cout, int pool_flags, int dt, int y_dt);
+int sfod_conv_first_bn_apply(const void* x, const void* w, const float* bias, const float* mean, const float* invstd,
+                             const float* gamma, const float* beta, void* z, int B, int H, int W, int ldz, int dt,
+                             void* stream);
+int sfod_set_first_apply_recompute(int on);
 
 /* weight gradient: dw[n][tap][c] += sum_m dy[m][n] * x[pix(m)+tap][c]  (fp32, packed layout, added
  * into the caller's (zero-initialised) buffer).  3x3 bf16 layers run the halo-patch kernel: pixel

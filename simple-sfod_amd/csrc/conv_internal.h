@@ -89,7 +89,16 @@ void sfod_f16_poll_cda(unsigned* out, hipStream_t s);
 
 // ---- first layer (Cin = one padded chunk of 8, Cout = 64), bf16 / bf16x3 ------------------------------------------
 int sfod_f1_nblk(int B, int H, int W);
-// y == nullptr: statistics only (no stores); scale / shift: optional per-channel affine before the activation
+// y == nullptr: statistics only (no stores); scale / shift: optional per-channel affine before the activation.
+// bn (bf16 pairs, y the z pairs, no scale / shift): the epilogue is sfod_bn_relu_pool_fwd's arithmetic (ReLU, no pooling) on
+// the fp32 value a launch without it stores -- z is bit-identical to that launch followed by the BatchNorm pass.
+bool sfod_f1_bn_ok(int W);      // the BatchNorm epilogue's loop keeps 32-bit patch offsets
+struct F1BnApply {
+  const float* mean;
+  const float* invstd;
+  const float* gamma;
+  const float* beta;
+};
 int sfod_f1_launch(const void* x, const void* w, const float* bias, void* y, float* stats, int B, int H, int W,
                    int ldy, int act, hipStream_t s, const float* scale = nullptr, const float* shift = nullptr, int split = 0,
-                   const unsigned* wamax = nullptr);
+                   const unsigned* wamax = nullptr, const F1BnApply* bn = nullptr);

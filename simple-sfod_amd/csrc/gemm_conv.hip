@@ -787,11 +787,41 @@ extern "C" int sfod_conv_first_fused_ws(const void* x, const void* w, const uint
   SFOD_REQUIRE(conv_shape_fits(B, H, W, 8, 64, 3) && sfod_ints_ok({ldy}), "conv_first_fused: negative or oversized extent");
   SFOD_REQUIRE(x != nullptr && w != nullptr, "conv_first_fused: null operand");
   SFOD_REQUIRE(w_absmax == nullptr || dt == SFOD_F16X3, "conv_first: scaled weights are an SFOD_F16X3 format");
-  SFOD_REQUIRE(sfod_conv_first_supported(B, H, W, 8, 64, dt, ldy),
-               "conv_first_fused: shape not served by the first-layer kernel (sfod_conv_first_supported)");
+  // (the kernel serves every extent; sfod_conv_first_supported says where sfod_conv_fwd picks it)
+  SFOD_REQUIRE((dt == SFOD_BF16 || sfod_is_pairs(dt)) && ldy % 8 == 0,
+               "conv_first_fused: operands not served by the first-layer kernel (sfod_conv_first_supported)");
   SFOD_REQUIRE(y != nullptr || stats != nullptr, "conv_first_fused: nothing to produce");
   SFOD_REQUIRE((scale == nullptr) == (shift == nullptr), "conv_first_fused: scale and shift come together");
   return sfod_f1_launch(x, w, bias, y, stats, B, H, W, ldy, act, (hipStream_t)stream, scale, shift, split_code(dt), w_absmax);
+}
+
+extern "C" int sfod_conv_first_stats_blocks(int B, int H, int W) {
+  return conv_shape_fits(B, H, W, 8, 64, 3) ? sfod_f1_nblk(B, H, W) : 0;
+}
+
+// Student conv1_1, pass 2: the BatchNorm + ReLU apply pass by recomputing the K = 27 convolution instead of re-reading y
+static SfodKnob g_first_apply_recompute{"SFOD_FIRST_APPLY_RECOMPUTE", 1, sfod_knob_bool};
+extern "C" int sfod_set_first_apply_recompute(int on) { g_first_apply_recompute.set(on); return 0; }
+
+extern "C" int sfod_conv_first_bn_apply_supported(int B, int H, int W, int Cin, int Cout, int pool_flags, int dt, int y_dt) {
+  if (!g_first_apply_recompute.get() || !conv_shape_fits(B, H, W, Cin, Cout, 3)) return 0;
+  if (Cin != 8 || Cout != 64 || pool_flags != 0 || dt != SFOD_BF16X3 || y_dt != SFOD_F32 || !sfod_f1_bn_ok(W)) return 0;
+  // z equals the BatchNorm pass over sfod_conv_fwd's y only where that y comes from this kernel
+  return conv_query_plan(B, H, W, Cin, Cout, 3, dt).kind == CONV_FIRST ? 1 : 0;
+}
+
+extern "C" int sfod_conv_first_bn_apply(const void* x, const void* w, const float* bias, const float* mean,
+                                        const float* invstd, const float* gamma, const float* beta, void* z, int B, int H,
+                                        int W, int ldz, int dt, void* stream) {
+  sfod_note_conv_kernel(nullptr);
+  SFOD_REQUIRE(conv_shape_fits(B, H, W, 8, 64, 3) && sfod_ints_ok({ldz}), "conv_first_bn_apply: negative or oversized extent");
+  SFOD_REQUIRE(x != nullptr && w != nullptr && z != nullptr, "conv_first_bn_apply: null operand");
+  SFOD_REQUIRE(mean != nullptr && invstd != nullptr && gamma != nullptr && beta != nullptr,
+               "conv_first_bn_apply: null BatchNorm operand");
+  SFOD_REQUIRE(dt == SFOD_BF16X3 && ldz % 8 == 0 && ldz >= 64 && sfod_f1_bn_ok(W),
+               "conv_first_bn_apply: not served (sfod_conv_first_bn_apply_supported)");
+  const F1BnApply bn{mean, invstd, gamma, beta};
+  return sfod_f1_launch(x, w, bias, z, nullptr, B, H, W, ldz, 1, (hipStream_t)stream, nullptr, nullptr, 1, nullptr, &bn);
 }
 
 extern "C" int sfod_conv_fwd_scratch(const void* x, const void* w, const uint32_t* w_absmax, const float* bias, void* y,

@@ -290,8 +290,15 @@ class vgg_backbone(nn.Module):
                 continue
             # bf16x3 / f16x3: y is fp32, z is written as (hi, lo) pairs; a pass that will be differentiated also gets
             # the operand of the next layer's weight gradient from the same launch (f16x3: bf16 pairs; else z itself)
-            zz = native.bn_relu_pool_fwd(y, mean, invstd, bn.weight.detach(), bn.bias.detach(), pool,
-                                         out_dtype=x.dtype, with_grad_operand=save)
+            if li == 0 and save and native.conv_first_bn_apply_supported(x, y, cout, pool):
+                # student conv1_1: the apply pass recomputes the K = 27 convolution from the 8-channel input instead of
+                # re-reading the 64-channel y (which stays: the backward needs it) -- the same bits as the pass below
+                z = native.conv_first_bn_apply(x, wp, conv.bias.detach(), mean, invstd, bn.weight.detach(),
+                                               bn.bias.detach())
+                zz = (z, z)
+            else:
+                zz = native.bn_relu_pool_fwd(y, mean, invstd, bn.weight.detach(), bn.bias.detach(), pool,
+                                             out_dtype=x.dtype, with_grad_operand=save)
             z, z_g = zz if save else (zz, None)
             if save:
                 saved.append((x_g, y, mean, invstd))

@@ -866,6 +866,46 @@ def conv_first_apply(x, w_packed, bias, scale, shift, relu=True):
     return z
 
 
+def set_conv_first_pipe(on):
+    """bf16x3 / f16x3 first-layer kernel: 1 (default) the pipelined tile loop, 0 the plain one.  Same bits (A/B knob,
+    include/sfod_hip.h)."""
+    load().sfod_set_conv_first_pipe(int(on))
+
+
+def set_conv_first_grid(n):
+    """Cap the first-layer kernel's persistent grid at ``n`` workgroups (0: one per resident slot): several tiles per
+    workgroup on small images."""
+    load().sfod_set_conv_first_grid(int(n))
+
+
+def set_first_apply_recompute(on):
+    """Student conv1_1's BatchNorm + ReLU pass: 1 (default) by recomputing the convolution (``conv_first_bn_apply``), 0 the
+    elementwise pass over y.  Same bits either way (A/B knob, include/sfod_hip.h)."""
+    load().sfod_set_first_apply_recompute(int(on))
+
+
+def conv_first_bn_apply_supported(x, y, cout, pool, relu=True):
+    """whether ``conv_first_bn_apply`` reproduces ``bn_relu_pool_fwd(y, ...)`` (bf16 pairs out) for the layer with operand
+    ``x`` and pre-BatchNorm output ``y`` of ``conv_fwd`` (first layer, bf16 pairs, ReLU, no pooling)"""
+    if x.dim() != 4 or y.dim() != 4 or not x.is_cuda or tuple(y.shape) != (*x.shape[:3], cout):
+        return False
+    if x.dtype not in PAIR_DTYPES:
+        return False
+    B, H, W, cin = x.shape
+    return bool(query("sfod_conv_first_bn_apply_supported", B, H, W, cin, cout, int(pool) | (0 if relu else 2), dt_of(x),
+                      dt_of(y)))
+
+
+def conv_first_bn_apply(x, w_packed, bias, mean, invstd, gamma, beta):
+    """z = relu(bn(conv(x) + bias)) [B,H,W,64] as bf16 pairs, the convolution recomputed: bit-identical to
+    ``bn_relu_pool_fwd(conv_fwd(x, ...), mean, invstd, gamma, beta, False, out_dtype=x.dtype)`` where
+    ``conv_first_bn_apply_supported`` holds."""
+    B, H, W, cin = x.shape
+    z = torch.empty(B, H, W, 64, dtype=x.dtype, device=x.device)
+    call("sfod_conv_first_bn_apply", x, w_packed, bias, mean, invstd, gamma, beta, z, B, H, W, 64, dt_of(x))
+    return z
+
+
 _ws_cache = {}
 
 
