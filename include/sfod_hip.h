@@ -821,6 +821,32 @@ int sfod_frcnn_finalize(const float* s_boxes, const float* sorted_scores, const 
                         int32_t* det_classes, int32_t* det_count, float* gt_boxes,
                         int32_t* gt_classes, int32_t* gt_count, void* stream);
 
+/* ---- TEST.AUG: the box merge of test-time augmentation (d2 GeneralizedRCNNWithTTA: _get_augmented_boxes and the entry of
+ * _merge_detections -> fast_rcnn_inference_single_image), one launch per batch of images, nothing read back ----
+ * Reads the det_* containers of sfod_frcnn_finalize for B images x A augmentations: det_boxes [B,A,cap,4] fp32 at the
+ * augmented pass's size, det_scores [B,A,cap], det_classes [B,A,cap] i32, det_count [B,A] (clamped to 0..cap; a slot at or
+ * beyond the count is never read).  aug_table [B,A,8] fp32 = (w_a, h_a, flip != 0, w / w_a, h / h_a, W0 / w, H0 / h, unused):
+ * the augmented tensor's size, whether it was mirrored, and the two ratio pairs, each the double quotient rounded to fp32
+ * once.  image_sizes [B,2] i32 = (H0, W0), the frame the detections go back to.  Per live slot, in fp32 without contraction:
+ *   1. the inverse transforms in reverse order, each on the corners with min / max as d2's Transform.apply_box does:
+ *      x -> w_a - x when mirrored; (x, y) * (w / w_a, h / h_a); (x, y) * (W0 / w, H0 / h) -- two separate multiplications;
+ *   2. dropped when a coordinate (before or after 1.) or the score is not finite, or the class is outside [0, K);
+ *   3. clipped to [0, W0] x [0, H0];  4. kept when score > score_thresh (strict).
+ * Writes the COMPACT candidates in concatenation order (augmentation, then slot): cand_boxes [B,A*cap,4], cand_scores
+ * [B,A*cap] (-1 for a slot that is dead or dropped, box and class 0), cand_classes [B,A*cap] i32, cand_count [B] = the number
+ * kept (a workgroup sum in fixed order; no atomics).  After sfod_segmented_sort_desc on cand_scores the chain continues with
+ * sfod_frcnn_prepare_nms_cls -> sfod_nms -> sfod_frcnn_finalize.  SFOD_EBADARG before any launch: a NULL pointer, B outside
+ * 1..65535, A outside 1..64, cap < 1, A * cap > 4096, K < 1, a non-finite score_thresh. */
+int sfod_tta_merge(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                   const int32_t* det_count, const float* aug_table, const int32_t* image_sizes, int B, int A, int cap,
+                   int K, float score_thresh, float* cand_boxes, float* cand_scores, int32_t* cand_classes,
+                   int32_t* cand_count, void* stream);
+/* sfod_frcnn_prepare_nms for compact candidates: the class of a candidate is cand_classes [B,n] at its index, not
+ * index % K.  One kernel pair serves both forms.  SFOD_EBADARG before any launch: a NULL pointer, B outside 1..65535, n < 1. */
+int sfod_frcnn_prepare_nms_cls(const float* cand_boxes, const int32_t* cand_classes, const int32_t* sorted_idx,
+                               const int32_t* cand_count, int B, int n, int numel_limit, float* s_boxes,
+                               float* s_alt_boxes, int32_t* s_classes, int32_t* mode, float* maxcoord_ws, void* stream);
+
 /* BPC calibration metric of the student's training pass (SURVEY 8a row a6 + 8f rank 4), logged as
  * calibration/bpc_loss and weighted by 0 (source_free_adaptive_teacher.py:549-550,566).  Fuses
  * SourceFreeFastRCNNOutputLayers.convert_bbox_scores (daod/modeling/roi_heads/source_free_fast_rcnn.py:15-36,

@@ -293,6 +293,9 @@ def get_cfg():
     _C.TEST.EVAL_PERIOD = 0
     _C.TEST.DETECTIONS_PER_IMAGE = 100
     _C.TEST.PRECISE_BN = CN({"ENABLED": False, "NUM_ITER": 200})
+    # d2's test-time augmentation (GeneralizedRCNNWithTTA; modeling/tta.py, validated by modeling/tta_options.py)
+    _C.TEST.AUG = CN({"ENABLED": False, "MIN_SIZES": (400, 500, 600, 700, 800, 900, 1000, 1100, 1200), "MAX_SIZE": 4000,
+                      "FLIP": True})
 
     _C.OUTPUT_DIR = "./output"
     _C.SEED = -1

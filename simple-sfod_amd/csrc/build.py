@@ -30,6 +30,7 @@ SOURCES = {
     "mosaic.hip": [],
     "da_losses.hip": ["-ffp-contract=off"],
     "cda_condition.hip": ["-ffp-contract=off"],
+    "tta_merge.hip": ["-ffp-contract=off"],
     "runtime.cpp": [],
 }
 HEADERS = ["common.h", "conv_internal.h", os.path.join("..", "..", "include", "sfod_hip.h")]

@@ -1629,8 +1629,8 @@ extern "C" int sfod_predict_probs(const float* scores, int ld, int R, int K, flo
 
 __global__ void __launch_bounds__(256)
 k_frcnn_gather(const float* __restrict__ cboxes, const int32_t* __restrict__ sidx,
-               const int32_t* __restrict__ ccount, int n, int K, float* __restrict__ sboxes,
-               int32_t* __restrict__ scls, float* maxcoord) {
+               const int32_t* __restrict__ ccount, int n, int K, const int32_t* __restrict__ ccls,
+               float* __restrict__ sboxes, int32_t* __restrict__ scls, float* maxcoord) {
   const int b = blockIdx.y;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   float mx = 0.f;
@@ -1638,7 +1638,8 @@ k_frcnn_gather(const float* __restrict__ cboxes, const int32_t* __restrict__ sid
     const int idx = sidx[(int64_t)b * n + j];
     Box bx = load_box(cboxes + ((int64_t)b * n + idx) * 4);
     store_box(sboxes + ((int64_t)b * n + j) * 4, bx);
-    scls[(int64_t)b * n + j] = idx % K;
+    // [B, P*K] candidates carry the class in the index; compact candidates (sfod_tta_merge) carry it beside the box
+    scls[(int64_t)b * n + j] = ccls ? ccls[(int64_t)b * n + idx] : idx % K;
     if (j < ccount[b]) mx = fmaxf(fmaxf(bx.x1, bx.y1), fmaxf(bx.x2, bx.y2));
   }
   mx = wave_max(mx);
@@ -1660,22 +1661,42 @@ k_frcnn_offset(const float* __restrict__ sboxes, const int32_t* __restrict__ scl
   store_box(alt + ((int64_t)b * n + j) * 4, Box{bx.x1 + off, bx.y1 + off, bx.x2 + off, bx.y2 + off});
 }
 
-extern "C" int sfod_frcnn_prepare_nms(const float* cand_boxes, const float* sorted_scores,
-                                      const int32_t* sorted_idx, const int32_t* cand_count, int B, int n,
-                                      int K, int numel_limit, float* s_boxes, float* s_alt_boxes,
-                                      int32_t* s_classes, int32_t* mode, float* maxcoord_ws, void* stream) {
-  SFOD_REQUIRE_EXTENTS("frcnn_prepare_nms", B, n, K, numel_limit);
-  (void)sorted_scores;
-  hipStream_t s = (hipStream_t)stream;
+static int frcnn_prepare_nms(const float* cand_boxes, const int32_t* cand_classes, const int32_t* sorted_idx,
+                             const int32_t* cand_count, int B, int n, int K, int numel_limit, float* s_boxes,
+                             float* s_alt_boxes, int32_t* s_classes, int32_t* mode, float* maxcoord_ws, hipStream_t s) {
   (void)hipMemsetAsync(maxcoord_ws, 0, sizeof(float) * B, s);
   dim3 grid(cdiv(n, 256), B);
-  hipLaunchKernelGGL(k_frcnn_gather, grid, dim3(256), 0, s, cand_boxes, sorted_idx, cand_count, n, K,
+  hipLaunchKernelGGL(k_frcnn_gather, grid, dim3(256), 0, s, cand_boxes, sorted_idx, cand_count, n, K, cand_classes,
                      s_boxes, s_classes, maxcoord_ws);
   int rc = sfod_check_launch("frcnn_gather");
   if (rc) return rc;
   hipLaunchKernelGGL(k_frcnn_offset, grid, dim3(256), 0, s, s_boxes, s_classes, cand_count, n,
                      numel_limit, maxcoord_ws, s_alt_boxes, mode);
   return sfod_check_launch("frcnn_offset");
+}
+
+extern "C" int sfod_frcnn_prepare_nms(const float* cand_boxes, const float* sorted_scores,
+                                      const int32_t* sorted_idx, const int32_t* cand_count, int B, int n,
+                                      int K, int numel_limit, float* s_boxes, float* s_alt_boxes,
+                                      int32_t* s_classes, int32_t* mode, float* maxcoord_ws, void* stream) {
+  SFOD_REQUIRE_EXTENTS("frcnn_prepare_nms", B, n, K, numel_limit);
+  (void)sorted_scores;
+  return frcnn_prepare_nms(cand_boxes, nullptr, sorted_idx, cand_count, B, n, K, numel_limit, s_boxes, s_alt_boxes,
+                           s_classes, mode, maxcoord_ws, (hipStream_t)stream);
+}
+
+extern "C" int sfod_frcnn_prepare_nms_cls(const float* cand_boxes, const int32_t* cand_classes,
+                                          const int32_t* sorted_idx, const int32_t* cand_count, int B, int n,
+                                          int numel_limit, float* s_boxes, float* s_alt_boxes, int32_t* s_classes,
+                                          int32_t* mode, float* maxcoord_ws, void* stream) {
+  SFOD_REQUIRE_EXTENTS("frcnn_prepare_nms_cls", B, n, numel_limit);
+  SFOD_REQUIRE(B >= 1 && B <= 65535 && n >= 1, "frcnn_prepare_nms_cls: B in 1..65535 and n >= 1");
+  SFOD_REQUIRE(cand_boxes != nullptr && cand_classes != nullptr && sorted_idx != nullptr && cand_count != nullptr &&
+                   s_boxes != nullptr && s_alt_boxes != nullptr && s_classes != nullptr && mode != nullptr &&
+                   maxcoord_ws != nullptr,
+               "frcnn_prepare_nms_cls: null argument");
+  return frcnn_prepare_nms(cand_boxes, cand_classes, sorted_idx, cand_count, B, n, 1, numel_limit, s_boxes, s_alt_boxes,
+                           s_classes, mode, maxcoord_ws, (hipStream_t)stream);
 }
 
 __global__ void __launch_bounds__(128)

@@ -534,6 +534,19 @@ class BaseTrainer:
             results = list(results.values())[0]
         return results
 
+    @classmethod
+    def test_with_TTA(cls, cfg, model):
+        """d2's ``DefaultTrainer`` example: the model behind ``GeneralizedRCNNWithTTA`` (modeling/tta.py), ``cls.test`` with
+        the evaluators built for ``<OUTPUT_DIR>/inference_TTA``, every result key suffixed ``_TTA``."""
+        from collections import OrderedDict
+        from ..modeling.tta import GeneralizedRCNNWithTTA
+        wrapped = GeneralizedRCNNWithTTA(cfg, model)
+        names = list(cfg.DATASETS.TEST) or ["synthetic_test"]
+        folder = os.path.join(cfg.OUTPUT_DIR, "inference_TTA") if cfg.OUTPUT_DIR else None
+        evaluators = [cls.build_evaluator(cfg, name, output_folder=folder) for name in names]
+        res = cls.test(cfg, wrapped, evaluators)
+        return OrderedDict({k + "_TTA": v for k, v in res.items()})
+
     # ---- step ----------------------------------------------------------------------------------------
     def step_stream(self):
         """``with trainer.step_stream(): <loop of run_step()>`` -- see ``_on_step_stream``; ``train()`` and bench.py use it"""

@@ -125,12 +125,15 @@ class GeneralizedRCNN(nn.Module):
         return losses
 
     @torch.no_grad()
-    def inference(self, batched_inputs, do_postprocess=True):
+    def inference(self, batched_inputs, do_postprocess=True, as_instances=True):
+        """``as_instances=False`` (with ``do_postprocess=False``): the ROI heads' fixed-capacity ``BatchedDetections`` instead
+        of ``list[Instances]`` -- no host synchronisation (modeling/tta.py hands them to the merge kernel)."""
         assert not self.training
+        assert as_instances or not do_postprocess, "detector_postprocess works on Instances"
         images = self.preprocess_image(batched_inputs)
         features = self._features(images)
         proposals, _ = self.proposal_generator(images, features, None, as_instances=False)
-        results, _ = self.roi_heads(images, features, proposals, None)
+        results, _ = self.roi_heads(images, features, proposals, None, as_instances=as_instances)
         if not do_postprocess:
             return results
         out = []

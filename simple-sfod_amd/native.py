@@ -1738,6 +1738,62 @@ def frcnn_inference(pred, K, props, prop_count, sizes, score_thresh, nms_thresh,
     return out
 
 
+TTA_ROW = 8               # floats per (image, augmentation) row of sfod_tta_merge's table
+TTA_MAX_AUG, TTA_MAX_CAND = 64, 4096      # include/sfod_hip.h: A <= 64, A * cap <= 4096
+
+
+def tta_merge_candidates(det_boxes, det_scores, det_classes, det_count, aug_table, sizes, K, score_thresh):
+    """sfod_tta_merge: containers of B images x A augmentations ([B,A,cap,4] / [B,A,cap] / [B,A,cap] i32 / [B,A] i32), the
+    transform table [B,A,8] fp32 and (H0, W0) [B,2] i32 -> compact candidates in the original frame, concatenation order:
+    (cand_boxes [B,A*cap,4], cand_scores [B,A*cap] with -1 in filtered slots, cand_classes [B,A*cap] i32, cand_count [B])."""
+    B, A, cap = det_scores.shape
+    dev = det_boxes.device
+    assert det_boxes.dtype == torch.float32 and det_scores.dtype == torch.float32 and aug_table.dtype == torch.float32
+    assert det_classes.dtype == torch.int32 and det_count.dtype == torch.int32 and sizes.dtype == torch.int32
+    assert det_boxes.shape == (B, A, cap, 4) and det_classes.shape == (B, A, cap) and det_count.shape == (B, A)
+    assert aug_table.shape == (B, A, TTA_ROW) and sizes.shape == (B, 2)
+    n = A * cap
+    cb = torch.empty(B, n, 4, dtype=torch.float32, device=dev)
+    cs = torch.empty(B, n, dtype=torch.float32, device=dev)
+    ck = torch.empty(B, n, dtype=torch.int32, device=dev)
+    cc = torch.empty(B, dtype=torch.int32, device=dev)
+    call("sfod_tta_merge", det_boxes, det_scores, det_classes, det_count, aug_table, sizes, B, A, cap, int(K),
+         float(score_thresh), cb, cs, ck, cc)
+    return cb, cs, ck, cc
+
+
+def tta_merge(det_boxes, det_scores, det_classes, det_count, aug_table, sizes, K, score_thresh, nms_thresh, max_det,
+              numel_limit=20000):
+    """The whole merge of test-time augmentation on the device: sfod_tta_merge, then the teacher post-processing's own
+    sort -> prepare (compact form) -> class-wise NMS -> top ``max_det``.  -> dict of det_boxes [B,max_det,4], det_scores,
+    det_classes, det_count at (H0, W0), plus the candidates (``cand_*``) for whoever checks them."""
+    cb, cs, ck, cc = tta_merge_candidates(det_boxes, det_scores, det_classes, det_count, aug_table, sizes, K, score_thresh)
+    B, n = cs.shape
+    dev = cs.device
+    ss, si = segmented_sort_desc(cs)
+    sb = torch.empty(B, n, 4, dtype=torch.float32, device=dev)
+    sa = torch.empty(B, n, 4, dtype=torch.float32, device=dev)
+    sc = torch.empty(B, n, dtype=torch.int32, device=dev)
+    mode = torch.empty(B, dtype=torch.int32, device=dev)
+    mx = torch.empty(B, dtype=torch.float32, device=dev)
+    call("sfod_frcnn_prepare_nms_cls", cb, ck, si, cc, B, n, int(numel_limit), sb, sa, sc, mode, mx)
+    keep_idx, keep_count = nms(sb, nms_thresh, max_det, n_per_image=cc, alt_boxes=sa, classes=sc, mode=mode)
+    out = {
+        "det_boxes": torch.empty(B, max_det, 4, dtype=torch.float32, device=dev),
+        "det_scores": torch.empty(B, max_det, dtype=torch.float32, device=dev),
+        "det_classes": torch.empty(B, max_det, dtype=torch.int32, device=dev),
+        "det_count": torch.empty(B, dtype=torch.int32, device=dev),
+        "cand_boxes": cb, "cand_scores": cs, "cand_classes": ck, "cand_count": cc, "mode": mode,
+    }
+    # (the pseudo-label outputs of the finalize kernel are not wanted here: a threshold nothing passes, scratch arrays)
+    gb = torch.empty(B, max_det, 4, dtype=torch.float32, device=dev)
+    gc = torch.empty(B, max_det, dtype=torch.int32, device=dev)
+    gn = torch.empty(B, dtype=torch.int32, device=dev)
+    call("sfod_frcnn_finalize", sb, ss, sc, keep_idx, keep_count, B, n, max_det, float("inf"), out["det_boxes"],
+         out["det_scores"], out["det_classes"], out["det_count"], gb, gc, gn)
+    return out
+
+
 def bpc_loss(pred, K, rois, roi_cls, sizes_dev, gt_boxes, gt_classes, gt_count, iou_thresh=0.5, box_reg=None,
              cls_loss=None):
     """BPC calibration scalar of one training pass (fused convert_bbox_scores + bpc_loss) -> 0-dim tensor."""

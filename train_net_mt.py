@@ -60,6 +60,8 @@ def main():
         # base.adabn_refinement(cfg, model): reset BN statistics, <= 1400 forward passes, Trainer.test, save "adabn"
         results = sfod.engine.test_refinement(cfg, model, loader, max_iters=args.adabn_iters, trainer_cls=Trainer,
                                                precise=args.adabn_precise)
+        if cfg.TEST.AUG.ENABLED:                         # d2 train_net.py: res.update(Trainer.test_with_TTA(cfg, model))
+            results.update(Trainer.test_with_TTA(cfg, model))
         if rank == 0:
             print(results)
         return results
