@@ -892,6 +892,38 @@ int sfod_f1_count(const float* det_boxes, const float* det_scores, const int32_t
                   const int32_t* gt_count, const float* scale, const int32_t* clip_size, int B, int D, int G, int K,
                   double iou, int top_n, float score, int32_t* counts, void* stream);
 
+/* COCOeval's per-image matching (pycocotools computeIoU + evaluateImg for boxes, as evaluation.py::COCOevalBBox.evaluate /
+ * _evaluate_img state it -- that code is the definition), one launch per batch, one wavefront per image, nothing read back.
+ * Only detections and ground truths of equal category in [0, K) meet.
+ *   det_boxes [B,D,4] fp32 XYXY as the model returned them, det_scores [B,D] fp32, det_classes [B,D] i32, det_count [B];
+ *   gt_boxes [B,G,4] f64 XYWH, gt_area [B,G] f64 (the annotation's own field, need not be w * h), gt_classes [B,G] i32,
+ *   gt_iscrowd [B,G] i32, gt_count [B].  Counts above D / G are clamped, entries beyond the counts are never read.
+ *   iou_thrs [T] and area_rng [A][2] = (lo, hi) are HOST arrays of doubles (they must be readable by the calling thread: the
+ *   entry point validates and copies them before it returns); they travel in the launch arguments by value and
+ *   are never recomputed on the device.
+ *   1. order: inside one (image, category) descending score, stable (equal scores keep index order, a NaN score ranks behind
+ *      every number, as numpy's mergesort of -score leaves it).  rank [B,D] i32 = the position in that order; -1 for a slot
+ *      beyond the count or a class outside [0, K) (its match / ignore words are 0).
+ *   2. detection w = x2 - x1, h = y2 - y1 in fp32; everything after that in fp64 without contraction, IEEE division.
+ *   3. IoU: extents min(dx + dw, gx + gw) - max(dx, gx) and the same in y; 0 when either is <= 0; otherwise
+ *      inter / ((da + ga) - inter), for a crowd ground truth inter / da, with da = dw * dh and ga = gw * gh.
+ *   4. per area range a a ground truth is ignored when it is crowd or gt_area < lo or gt_area > hi; ground truths are visited
+ *      not-ignored first, each group in annotation order.
+ *   5. per threshold t the greedy loop: start from iou = min(t, 1 - 1e-10); skip a ground truth already matched and not
+ *      crowd; stop when a not-ignored match is held and the next ground truth is ignored; skip when its IoU < iou (equality
+ *      passes: on equal IoU the later-visited one replaces the earlier); otherwise it becomes the match and iou its IoU.
+ *   6. bit a * T + t of match [B,D] u64: the detection matched.  The same bit of ignore [B,D] u64: it matched an ignored
+ *      ground truth, or it is unmatched and dw * dh < lo or > hi.
+ *   7. npig [B,K,A] i32: the ground truths of class k that are not ignored in area range a.
+ * Every output element is written; plain vector stores, no atomics.  SFOD_EBADARG before any launch, outputs untouched: a NULL
+ * pointer, A < 1, T < 1, A * T > 64, D outside 1..100, G outside 1..256, K < 1, a non-finite threshold or range.
+ * B == 0 is a valid call that launches nothing. */
+int sfod_coco_match(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                    const int32_t* det_count, const double* gt_boxes, const double* gt_area, const int32_t* gt_classes,
+                    const int32_t* gt_iscrowd, const int32_t* gt_count, int B, int D, int G, int K, const double* iou_thrs,
+                    int T, const double* area_rng, int A, int32_t* rank, uint64_t* match, uint64_t* ignore, int32_t* npig,
+                    void* stream);
+
 /* Class-wise adaptive pseudo-label threshold: AdaptiveConfidenceBasedSelfTrainingLoss
  * (daod/modeling/adaptive_thresh/adaptive_confidence.py:6-34, "convex" curve) with the trainer's bookkeeping
  * (daod/engine/trainers/source_free_adaptive_teacher.py:282-295 count_label_prediction, :297-309

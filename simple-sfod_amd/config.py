@@ -413,6 +413,11 @@ def add_native_config(cfg):
                           alone -> ``{"bbox": {...}}``.  ("coco", "f1") is the reference's list (base.py:133-151): a
                           ``DatasetEvaluators`` of it and the ``F1Evaluator`` -> ``"bbox"`` and ``"F1 Score"``.  An
                           unknown name, a repeated name or an empty tuple is a ValueError.
+    SFOD.COCO_EVAL_DEVICE bool.  False (default): the "coco" evaluator is the host code, call for call.  True:
+                          ``NewCOCOEvaluator(device_match=True)``, alone and inside ("coco", "f1"): CUDA detections are packed
+                          on the device and matched by ``sfod_coco_match`` (COCOeval's per-image rule), ``evaluate()`` makes
+                          one copy; host tensors (MODEL.DEVICE cpu) keep the host path.  At most 100 detections and 256
+                          ground-truth boxes per image (a ValueError otherwise).  Anything but a bool is a ValueError.
     """
     _C = cfg
     _C.SFOD = CN()
@@ -455,6 +460,8 @@ def add_native_config(cfg):
     _C.SFOD.PRECISE_BN = CN({"SYNC": False})
     # the evaluators of Trainer.test, by name: "coco" (NewCOCOEvaluator), "f1" (F1Evaluator, counted on the device)
     _C.SFOD.EVALUATORS = ("coco",)
+    # COCOeval's matching on the device (sfod_coco_match) instead of the host loops; the "coco" evaluator only
+    _C.SFOD.COCO_EVAL_DEVICE = False
     # json file {"<dataset name>": {"json_file": ..., "image_root": ...}}: COCO-format datasets for the names in
     # DATASETS.*; names that are not registered fall back to the synthetic set (data/coco.py)
     _C.SFOD.DATASETS_FILE = ""

@@ -31,6 +31,7 @@ SOURCES = {
     "da_losses.hip": ["-ffp-contract=off"],
     "cda_condition.hip": ["-ffp-contract=off"],
     "tta_merge.hip": ["-ffp-contract=off"],
+    "coco_match.hip": ["-ffp-contract=off"],
     "runtime.cpp": [],
 }
 HEADERS = ["common.h", "conv_internal.h", os.path.join("..", "..", "include", "sfod_hip.h")]

@@ -488,7 +488,8 @@ class BaseTrainer:
         """``NewCOCOEvaluator`` for the "coco" evaluator type (base.py:133-142); the synthetic target set
         stands in for the registered datasets (no dataset files in the build environment).  ``SFOD.EVALUATORS`` names
         what is built: the default ("coco",) returns that evaluator itself, more than one name a ``DatasetEvaluators``
-        (("coco", "f1") is the reference's list, base.py:149)."""
+        (("coco", "f1") is the reference's list, base.py:149).  ``SFOD.COCO_EVAL_DEVICE`` True builds the "coco" evaluator
+        with ``device_match=True`` (its matching in ``sfod_coco_match``)."""
         from ..data import CITYSCAPES_CLASSES, TestLoader
         from ..evaluation import DatasetEvaluators, F1Evaluator, NewCOCOEvaluator
         kinds = tuple(cfg.SFOD.EVALUATORS)
@@ -497,13 +498,19 @@ class BaseTrainer:
         for kind in kinds:
             if kind not in ("coco", "f1") or kinds.count(kind) > 1:
                 raise ValueError(f"SFOD.EVALUATORS: unknown or repeated evaluator {kind!r} in {kinds} (built: 'coco', 'f1')")
+        on_device = cfg.SFOD.COCO_EVAL_DEVICE
+        if not isinstance(on_device, bool):
+            raise ValueError(f"SFOD.COCO_EVAL_DEVICE must be True or False, got {on_device!r}")
 
         def coco():
             loader = data_loader or TestLoader(cfg, torch.device("cpu"), dataset_name=dataset_name)
             names = getattr(loader.dataset, "class_names", None) or CITYSCAPES_CLASSES[: cfg.MODEL.ROI_HEADS.NUM_CLASSES]
             if len(names) < cfg.MODEL.ROI_HEADS.NUM_CLASSES:
                 names = [str(i) for i in range(cfg.MODEL.ROI_HEADS.NUM_CLASSES)]
-            return NewCOCOEvaluator(dataset_name, loader.dataset.dataset_dicts(cfg), names, output_dir=output_folder)
+            if not on_device:
+                return NewCOCOEvaluator(dataset_name, loader.dataset.dataset_dicts(cfg), names, output_dir=output_folder)
+            return NewCOCOEvaluator(dataset_name, loader.dataset.dataset_dicts(cfg), names, output_dir=output_folder,
+                                    device_match=True)
 
         built = [coco() if kind == "coco" else F1Evaluator(cfg.MODEL.ROI_HEADS.NUM_CLASSES) for kind in kinds]
         return built[0] if len(built) == 1 else DatasetEvaluators(built)

@@ -11,10 +11,14 @@ Host-side numpy like the reference's (the model's forward is the device work); n
 The reference also appends an ``F1Evaluator`` (``base.py:149``): built here as ``F1Evaluator`` (below), the one evaluator
 that counts on the device (``sfod_f1_count``) and reads back once, in ``evaluate()``; ``SFOD.EVALUATORS ("coco", "f1")``
 puts both behind ``DatasetEvaluators`` as the reference does.
+``SFOD.COCO_EVAL_DEVICE`` (``NewCOCOEvaluator(device_match=True)``) moves COCOeval's matching to the device the same way:
+``process`` packs the batch, ``sfod_coco_match`` applies ``COCOevalBBox._evaluate_img``'s rule per image, ``evaluate()`` makes
+one copy and hands ``accumulate()`` what it consumes.  ``COCOevalBBox.evaluate`` stays the definition of that rule.
 """
 import copy
 import itertools
 import logging
+import time
 from collections import OrderedDict, defaultdict
 
 import numpy as np
@@ -28,6 +32,8 @@ IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=
 REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
 MAX_DETS = [1, 10, 100]
 AREA_RNG = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
+COCO_DET_CAP = MAX_DETS[-1]       # detections per image the device path packs (TEST.DETECTIONS_PER_IMAGE's default)
+COCO_GT_CAP = 256                 # ground truths per image the device path packs (sfod_coco_match: G <= 256)
 
 
 def bbox_iou_xywh(dt, gt, iscrowd):
@@ -194,16 +200,54 @@ def instances_to_coco_json(instances, img_id):
             for k in range(len(scores))]
 
 
+def coco_compact(image_ids, det_count, det_scores, det_classes, rank, match, ignore, npig):
+    """What ``sfod_coco_match`` leaves of a set of images, without the padding: a dict of numpy arrays keyed by image id.
+    ``image_id`` (list, I entries), ``count`` [I] i32, ``npig`` [I,K,A] i32, and per detection below its image's count
+    (N = sum of the counts, image after image, index order) ``det_image`` (the row in ``image_id``), ``det_class``,
+    ``det_score`` f32, ``det_rank`` (-1: in no category), ``det_match`` / ``det_ignore`` u64 (bit a * T + t)."""
+    count = np.clip(np.asarray(det_count, dtype=np.int32).reshape(-1), 0, np.asarray(rank).shape[1])
+    I, D = np.asarray(rank).shape
+    assert len(image_ids) == I == len(count)
+    img, slot = np.nonzero(np.arange(D)[None, :] < count[:, None])
+    return {"image_id": list(image_ids), "count": count, "npig": np.asarray(npig, dtype=np.int32).reshape(I, *np.shape(npig)[1:]),
+            "det_image": img.astype(np.int32), "det_class": np.asarray(det_classes, dtype=np.int32)[img, slot],
+            "det_score": np.asarray(det_scores, dtype=np.float32)[img, slot], "det_rank": np.asarray(rank, dtype=np.int32)[img, slot],
+            "det_match": np.asarray(match).view(np.uint64)[img, slot], "det_ignore": np.asarray(ignore).view(np.uint64)[img, slot]}
+
+
+def coco_compact_merge(parts):
+    """The compact arrays of several shares (the ranks', in rank order) as one: rows appended, ``det_image`` shifted."""
+    parts = [p for p in parts if len(p["image_id"])]
+    if len(parts) == 1:
+        return parts[0]
+    if not parts:
+        raise ValueError("coco_compact_merge: nothing to merge")
+    base = np.cumsum([0] + [len(p["image_id"]) for p in parts[:-1]])
+    out = {"image_id": list(itertools.chain(*[p["image_id"] for p in parts])),
+           "det_image": np.concatenate([p["det_image"] + np.int32(b) for p, b in zip(parts, base)])}
+    for k in ("count", "npig", "det_class", "det_score", "det_rank", "det_match", "det_ignore"):
+        out[k] = np.concatenate([p[k] for p in parts])
+    return out
+
+
 class NewCOCOEvaluator:
     """``NewCOCOEvaluator(dataset_name, output_dir=...)`` (``new_cocoevaluator.py:33``): d2's ``reset`` /
     ``process`` / ``evaluate`` protocol; ``evaluate`` returns ``OrderedDict(bbox={AP, AP50, AP75, APs, APm,
     APl, "AP-<class>", "AP-<class>_AP50"})`` in percent, NaN where undefined.  ``dataset_dicts`` are d2
-    dataset records (``annotations`` with ``bbox`` XYWH_ABS / ``category_id`` / ``iscrowd``)."""
+    dataset records (``annotations`` with ``bbox`` XYWH_ABS / ``category_id`` / ``iscrowd``).
+    ``device_match`` (``SFOD.COCO_EVAL_DEVICE``): CUDA instances are packed into fixed-capacity arrays next to their image's
+    rows of the ground-truth table and matched by ``native.coco_match`` -- no ``.cpu()``, no synchronisation in ``process``;
+    ``evaluate()`` copies the kernel's words once, rebuilds ``COCOevalBBox._eval_imgs`` from them and runs the same
+    ``accumulate`` / ``summarize``.  Host instances take the host path whatever the flag says; both kinds
+    in one round are a ``ValueError`` in ``evaluate()``.  ``timings`` holds the seconds
+    the last device-path ``evaluate()`` spent in the copy, the rebuild and ``accumulate`` + ``summarize``, ``coco_eval`` its
+    ``COCOevalBBox``."""
 
     METRICS = ["AP", "AP50", "AP75", "APs", "APm", "APl"]
 
-    def __init__(self, dataset_name, dataset_dicts, class_names, distributed=True, output_dir=None):
+    def __init__(self, dataset_name, dataset_dicts, class_names, distributed=True, output_dir=None, device_match=False):
         self.dataset_name, self.class_names = dataset_name, list(class_names)
+        self._device_match = bool(device_match)
         self._distributed, self._output_dir = distributed, output_dir
         self._gt = []
         self._img_ids = []
@@ -216,19 +260,184 @@ class NewCOCOEvaluator:
                 self._gt.append({"image_id": rec["image_id"], "category_id": int(ann["category_id"]),
                                  "bbox": [x, y, w, h], "iscrowd": int(ann.get("iscrowd", 0)),
                                  "area": float(ann.get("area", w * h))})
+        if self._device_match:
+            self._build_gt_table()
         self.reset()
 
     def reset(self):
         self._predictions = []
+        if self._device_match:
+            self._matched, self.timings = [], {}
+
+    def _build_gt_table(self):
+        """``self._gt`` as arrays, annotation order, and each image's rows in them (what ``process`` stages per batch)."""
+        n = len(self._gt)
+        self._gt_f64 = np.zeros((n, 5), dtype=np.float64)                    # bbox XYWH | area
+        self._gt_i32 = np.zeros((n, 2), dtype=np.int32)                      # category_id | iscrowd
+        rows = defaultdict(list)
+        for j, g in enumerate(self._gt):
+            self._gt_f64[j, :4], self._gt_f64[j, 4] = g["bbox"], g["area"]
+            self._gt_i32[j] = g["category_id"], g["iscrowd"]
+            rows[g["image_id"]].append(j)
+        self._gt_rows = {k: np.asarray(v, dtype=np.int64) for k, v in rows.items()}
+        for image_id, r in self._gt_rows.items():
+            if len(r) > COCO_GT_CAP:
+                raise ValueError(f"NewCOCOEvaluator(device_match=True): image {image_id!r} has {len(r)} ground-truth boxes, "
+                                 f"above the device path's cap of {COCO_GT_CAP}; use the host path (SFOD.COCO_EVAL_DEVICE False)")
 
     def process(self, inputs, outputs):
+        if self._device_match and len(outputs) and all("instances" in o and o["instances"].scores.is_cuda for o in outputs):
+            return self._process_device(inputs, outputs)
         for inp, out in zip(inputs, outputs):
             pred = {"image_id": inp["image_id"]}
             if "instances" in out:
                 pred["instances"] = instances_to_coco_json(out["instances"], inp["image_id"])
             self._predictions.append(pred)
 
+    def _process_device(self, inputs, outputs):
+        insts = [o["instances"] for o in outputs]
+        ids = [i["image_id"] for i in inputs]
+        B, D, G = len(insts), COCO_DET_CAP, COCO_GT_CAP
+        nds = [len(oi) for oi in insts]
+        for image_id, n in zip(ids, nds):
+            if n > D:
+                raise ValueError(f"NewCOCOEvaluator(device_match=True): image {image_id!r} has {n} detections, more than {D} "
+                                 "(TEST.DETECTIONS_PER_IMAGE); the host path truncates them per category, the device path refuses")
+        dev = insts[0].scores.device
+        N = sum(nds)
+        empty = np.zeros(0, dtype=np.int64)
+        grows = [self._gt_rows.get(i, empty) for i in ids]
+        # host numbers (tensor shapes, the evaluator's own table) are staged in pinned memory and uploaded without blocking;
+        # the detections' values never leave the device: one concatenation and one row scatter per field
+        ints = torch.empty(2 * B + 2 * B * G, dtype=torch.int32, pin_memory=True)   # det counts | gt counts | category | iscrowd
+        f64 = torch.empty(5 * B * G, dtype=torch.float64, pin_memory=True)          # bbox [B,G,4] | area [B,G]
+        rows = torch.empty(N, dtype=torch.int64, pin_memory=True)
+        ints_h, f64_h, rows_h = ints.numpy(), f64.numpy(), rows.numpy()
+        ints_h[:B], ints_h[B:2 * B] = nds, [len(r) for r in grows]
+        cat_h, crowd_h = ints_h[2 * B:2 * B + B * G].reshape(B, G), ints_h[2 * B + B * G:].reshape(B, G)
+        box_h, area_h = f64_h[:4 * B * G].reshape(B, G, 4), f64_h[4 * B * G:].reshape(B, G)
+        for b, r in enumerate(grows):
+            box_h[b, :len(r)], area_h[b, :len(r)] = self._gt_f64[r, :4], self._gt_f64[r, 4]
+            cat_h[b, :len(r)], crowd_h[b, :len(r)] = self._gt_i32[r, 0], self._gt_i32[r, 1]
+        if N:
+            rows_h[:] = np.concatenate([i * D + np.arange(n) for i, n in enumerate(nds)])
+        ints, f64, rows = (t.to(dev, non_blocking=True) for t in (ints, f64, rows))
+
+        def scatter(parts, dtype, *tail):
+            out = torch.empty(B * D, *tail, dtype=dtype, device=dev)
+            if N:
+                out.index_copy_(0, rows, torch.cat([p.detach() for p in parts]).to(device=dev, dtype=dtype, non_blocking=True))
+            return out.view(B, D, *tail)
+        db = scatter([oi.pred_boxes.tensor for oi in insts], torch.float32, 4)      # as the model returned them: no scale
+        ds = scatter([oi.scores for oi in insts], torch.float32)
+        dc = scatter([oi.pred_classes for oi in insts], torch.int32)
+        from . import native
+        rank, match, ignore, npig = native.coco_match(
+            db, ds, dc, ints[:B], f64[:4 * B * G].view(B, G, 4), f64[4 * B * G:].view(B, G),
+            ints[2 * B:2 * B + B * G].view(B, G), ints[2 * B + B * G:].view(B, G), ints[B:2 * B], len(self.class_names),
+            IOU_THRS, AREA_RNG)
+        self.add_matched(ids, ds, dc, ints[:B], rank, match, ignore, npig)
+
+    def add_matched(self, image_ids, det_scores, det_classes, det_count, rank, match, ignore, npig):
+        """Container-level entry: one batch's scores / classes / counts and what ``native.coco_match`` wrote for it (tensors of
+        any one device; they stay there until ``evaluate()``)."""
+        self._matched.append((list(image_ids), det_count, det_scores, det_classes, rank, match, ignore, npig))
+
+    def _compact(self):
+        """this rank's batches -> ``coco_compact`` arrays, through ONE device-to-host copy"""
+        if not self._matched:
+            K = len(self.class_names)
+            z = np.zeros((0, COCO_DET_CAP))
+            return coco_compact([], np.zeros(0), z, z, z, z.astype(np.int64), z.astype(np.int64), np.zeros((0, K, len(AREA_RNG))))
+        ids = list(itertools.chain(*[m[0] for m in self._matched]))
+        fields = [torch.cat([m[j] for m in self._matched]) for j in (5, 6, 4, 2, 3, 7, 1)]   # 8-byte words first: aligned views
+        flat = torch.cat([f.contiguous().view(-1).view(torch.uint8) for f in fields]).cpu().numpy()
+        out, at = [], 0
+        for f, dt in zip(fields, (np.int64, np.int64, np.int32, np.float32, np.int32, np.int32, np.int32)):
+            n = f.numel() * f.element_size()
+            out.append(flat[at:at + n].view(dt).reshape(tuple(f.shape)))
+            at += n
+        match, ignore, rank, scores, classes, npig, count = out
+        return coco_compact(ids, count, scores, classes, rank, match, ignore, npig)
+
+    def _eval_imgs_from_compact(self, c, coco_eval):
+        """``COCOevalBBox._eval_imgs`` (category x area range x image) as ``accumulate()`` reads it, from the compact arrays:
+        ``dtMatches`` nonzero where the bit is set, ``dtIgnore``, ``dtScores`` in the category's order, ``gtIgnore`` with one
+        zero per ground truth that counts."""
+        K, A, T, I0 = len(coco_eval.cat_ids), len(AREA_RNG), len(IOU_THRS), len(coco_eval.img_ids)
+        pos = {image_id: i for i, image_id in enumerate(coco_eval.img_ids)}
+        known = np.array([i in pos for i in c["image_id"]], dtype=bool)
+        ipos = np.array([pos.get(i, 0) for i in c["image_id"]], dtype=np.int64)
+        npig = np.zeros((I0, K, A), dtype=np.int64)
+        gt_any = np.zeros((I0, K), dtype=bool)
+        seen = np.zeros(I0, dtype=bool)
+        npig[ipos[known]], seen[ipos[known]] = c["npig"][known], True
+        lo, hi = np.array(AREA_RNG, dtype=np.float64).T
+        for g in self._gt:                                   # which (image, category) pairs have ground truth at all; the
+            i, k = pos.get(g["image_id"]), g["category_id"]  # counts of an image that no rank processed
+            if i is None or not 0 <= k < K:
+                continue
+            gt_any[i, k] = True
+            if not seen[i]:
+                npig[i, k] += ~(bool(g["iscrowd"]) | (g["area"] < lo) | (g["area"] > hi))
+        keep = (c["det_rank"] >= 0) & known[c["det_image"]] if len(c["det_rank"]) else np.zeros(0, dtype=bool)
+        di, dk, dr = ipos[c["det_image"][keep]], c["det_class"][keep].astype(np.int64), c["det_rank"][keep]
+        order = np.lexsort((dr, dk, di))
+        key = (di * K + dk)[order]
+        bits = np.arange(A * T, dtype=np.uint64)
+        words = lambda w: np.ascontiguousarray((((w[keep][order][:, None] >> bits) & np.uint64(1)) != 0).reshape(-1, A, T).transpose(1, 2, 0))
+        dtm, dtig = words(c["det_match"]).astype(np.float64), words(c["det_ignore"])
+        scores = c["det_score"][keep][order].astype(np.float64)
+        start = np.searchsorted(key, np.arange(I0 * K), side="left").reshape(I0, K)
+        end = np.searchsorted(key, np.arange(I0 * K), side="right").reshape(I0, K)
+        zeros = np.zeros(int(npig.max()) if npig.size else 0)
+        out = [None] * (K * A * I0)
+        for k in range(K):
+            for i in range(I0):
+                s, e = start[i, k], end[i, k]
+                if s == e and not gt_any[i, k]:
+                    continue
+                sc = scores[s:e]
+                for a in range(A):
+                    out[k * A * I0 + a * I0 + i] = {"dtMatches": dtm[a][:, s:e], "dtScores": sc, "gtIgnore": zeros[:npig[i, k, a]],
+                                                    "dtIgnore": dtig[a][:, s:e]}
+        return out
+
+    def _evaluate_matched(self):
+        t0 = time.perf_counter()
+        compact = self._compact()
+        t1 = time.perf_counter()
+        dist = torch.distributed
+        if self._distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            gathered = [None] * dist.get_world_size()
+            dist.all_gather_object(gathered, compact)
+            if dist.get_rank() != 0:
+                return {}
+            if any(len(p["image_id"]) for p in gathered):
+                compact = coco_compact_merge(gathered)
+        if len(compact["image_id"]) == 0:
+            logger.warning("[COCOEvaluator] Did not receive valid predictions.")
+            return {}
+        results = OrderedDict()
+        coco_eval = None
+        t2 = t3 = time.perf_counter()
+        if int(compact["count"].sum()) > 0:
+            coco_eval = COCOevalBBox(self._gt, [], range(len(self.class_names)), self._img_ids)
+            coco_eval._eval_imgs = self._eval_imgs_from_compact(compact, coco_eval)
+            t3 = time.perf_counter()
+            coco_eval.accumulate()
+            coco_eval.summarize()
+        self.coco_eval = coco_eval
+        self.timings = {"copy_s": t1 - t0, "rebuild_s": t3 - t2, "accumulate_s": time.perf_counter() - t3}
+        results["bbox"] = self._derive_coco_results(coco_eval, "bbox", self.class_names)
+        return copy.deepcopy(results)
+
     def evaluate(self):
+        if self._device_match and self._matched and self._predictions:
+            raise ValueError("NewCOCOEvaluator(device_match=True): batches of device tensors and of host tensors (or outputs "
+                             "without 'instances') were processed in one round; the two paths cannot be mixed")
+        if self._device_match and (self._matched or not self._predictions):
+            return self._evaluate_matched()
         preds = self._predictions
         if self._distributed and torch.distributed.is_available() and torch.distributed.is_initialized() \
                 and torch.distributed.get_world_size() > 1:

@@ -1831,6 +1831,43 @@ def f1_count(det_boxes, det_scores, det_classes, det_count, gt_boxes, gt_classes
     return counts
 
 
+COCO_MAX_DET, COCO_MAX_GT, COCO_MAX_BITS = 100, 256, 64      # include/sfod_hip.h: D <= 100, G <= 256, A * T <= 64
+
+
+def coco_match(det_boxes, det_scores, det_classes, det_count, gt_boxes, gt_area, gt_classes, gt_iscrowd, gt_count, K,
+               iou_thrs, area_rng, out=None):
+    """COCOeval's matching of a batch of fixed-capacity arrays (include/sfod_hip.h: sfod_coco_match; no host synchronisation)
+    -> (rank [B,D] i32, match [B,D] i64, ignore [B,D] i64, npig [B,K,A] i32); bit ``a * T + t`` of the two 64-bit words
+    belongs to area range ``a`` and threshold ``t`` (torch has no arithmetic on uint64: the words are held as int64).
+    ``iou_thrs`` [T] and ``area_rng`` [A][2] are host doubles, handed over by value.  ``out``: the four tensors to write."""
+    B, D = det_scores.shape
+    G = gt_classes.shape[1]
+    thrs = [float(t) for t in iou_thrs]
+    rng = [float(v) for lo_hi in area_rng for v in lo_hi]
+    T, A = len(thrs), len(rng) // 2
+    assert len(rng) == 2 * A
+    thrs_c, rng_c = (ctypes.c_double * T)(*thrs), (ctypes.c_double * (2 * A))(*rng)      # read by the call itself
+    assert det_boxes.dtype == torch.float32 and det_scores.dtype == torch.float32 and det_classes.dtype == torch.int32
+    assert gt_boxes.dtype == torch.float64 and gt_area.dtype == torch.float64 and gt_classes.dtype == torch.int32
+    assert gt_iscrowd.dtype == torch.int32 and det_count.dtype == torch.int32 and gt_count.dtype == torch.int32
+    assert det_boxes.shape == (B, D, 4) and det_classes.shape == (B, D) and det_count.shape == (B,)
+    assert gt_boxes.shape == (B, G, 4) and gt_area.shape == (B, G) and gt_iscrowd.shape == (B, G) and gt_count.shape == (B,)
+    dev = det_boxes.device
+    ins = (det_boxes, det_scores, det_classes, det_count, gt_boxes, gt_area, gt_classes, gt_iscrowd, gt_count)
+    # the kernel indexes dense arrays and loads a detection's box as one 16-byte word (call() checks contiguity too)
+    assert all(t.is_contiguous() and t.device == dev for t in ins), "coco_match: dense tensors of one device"
+    if out is None:
+        out = (torch.empty(B, D, dtype=torch.int32, device=dev), torch.empty(B, D, dtype=torch.int64, device=dev),
+               torch.empty(B, D, dtype=torch.int64, device=dev), torch.empty(B, int(K), A, dtype=torch.int32, device=dev))
+    rank, match, ignore, npig = out
+    assert rank.dtype == torch.int32 and match.dtype == torch.int64 and ignore.dtype == torch.int64 and npig.dtype == torch.int32
+    assert rank.shape == (B, D) and match.shape == (B, D) and ignore.shape == (B, D) and npig.shape == (B, int(K), A)
+    assert all(t.is_contiguous() and t.device == dev for t in out), "coco_match: dense outputs on the inputs' device"
+    call("sfod_coco_match", det_boxes, det_scores, det_classes, det_count, gt_boxes, gt_area, gt_classes, gt_iscrowd,
+         gt_count, B, D, G, int(K), ctypes.addressof(thrs_c), T, ctypes.addressof(rng_c), A, rank, match, ignore, npig)
+    return rank, match, ignore, npig
+
+
 def predict_probs(scores, cls_loss=None):
     """Row softmax of the class scores [R, K+1] (any row stride) in the teacher post-processing kernel's operation order;
     under ``cls_loss.sigmoid`` the sigmoid of every score."""
